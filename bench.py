@@ -11,6 +11,14 @@ Single-GPU steps are hipGraph-captured (one graph per pooled batch) unless
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1
 launched via torch.distributed.run with one rank per GPU. Rank 0 prints one
 JSON line with the whole-job examples/sec.
+
+A plain run does only what that line needs: set up, warm up, time the K
+steps, print. `--dump-outputs DIR` additionally writes what the last timed
+step returned (the per-row loss) as DIR/<name>.npy so two builds can be
+compared output for output; inputs and initial parameters are seeded, so the
+same arguments give the same inputs on every run. `--full` is reserved for
+secondary measurements (other models/precisions, baselines, per-kernel
+figures); there are none today, so it changes nothing yet.
 """
 
 from __future__ import annotations
@@ -21,6 +29,28 @@ import os
 import time
 
 import torch
+
+# --dump-outputs writes at most this many bytes in all; a larger output is
+# cut down to a fixed, seeded sample of its elements
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, named):
+    """Write {name: tensor} as out_dir/<name>.npy (float32, or float64 for
+    double outputs), sharing DUMP_BUDGET_BYTES evenly between the arrays."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    per_array = DUMP_BUDGET_BYTES // max(1, len(named))
+    for name, t in named.items():
+        t = t.detach().reshape(-1).cpu()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        cap = per_array // t.element_size()
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(20240229)
+            idx = torch.randperm(t.numel(), generator=g)[:cap].sort().values
+            t = t[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.numpy())
 
 
 def build_model(args, device, world):
@@ -157,6 +187,12 @@ def main():
                     help="N>1 layout: synchronous hash-sharded all-to-all, "
                          "or async PS (half the ranks serve shards, half "
                          "train; BASELINE config #5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (none today; "
+                         "a plain run times the headline figure only)")
     args = ap.parse_args()
 
     from lightctr_amd.data.synthetic import SyntheticCriteo
@@ -203,15 +239,17 @@ def main():
                 eager_step(i)
             torch.cuda.synchronize()
             graphs = []
+            graph_outs = []  # each graph's static output, refilled by replay
             for i in range(len(pool)):
                 gr = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gr):
-                    eager_step(i)
+                    graph_outs.append(eager_step(i))
                 graphs.append(gr)
             torch.cuda.synchronize()
 
             def graph_step(i):
                 graphs[i % len(graphs)].replay()
+                return graph_outs[i % len(graphs)]
 
             step = graph_step
         except Exception as e:  # capture unsupported -> eager fallback
@@ -234,8 +272,9 @@ def main():
     if have_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        step(i)
+        last = step(i)
         guard.step()
     if dist:
         dist.barrier()
@@ -243,6 +282,9 @@ def main():
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     guard.stop()
+    if args.dump_outputs and rank == 0 and last is not None:
+        # train_step hands its caller the per-row loss of that step
+        dump_outputs(args.dump_outputs, {"loss": last})
     # MAX over ranks
     if dist:
         t = torch.tensor([elapsed], device=device if have_gpu else "cpu")

@@ -1,6 +1,7 @@
 """Aux subsystem tests: ANN index, PCA, stats, ensembling, watchdog,
 persistent buffer, shm hashtable, batch predictor."""
 
+import os
 import time
 
 import pytest
@@ -14,6 +15,8 @@ from lightctr_amd.utils.persistent import PersistentBuffer, ShmHashTable
 from lightctr_amd.utils.stats import (normal_cdf, normal_cdf_inv,
                                       shuffle_pick_k, z_test)
 from lightctr_amd.utils.watchdog import Watchdog
+
+_REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_ann_index_recall():
@@ -461,7 +464,10 @@ def test_tools_importable():
     import ast
     import pathlib
 
-    for f in sorted(pathlib.Path("tools").glob("*.py")):
+    tools = pathlib.Path(__file__).resolve().parent.parent / "tools"
+    files = sorted(tools.glob("*.py"))
+    assert files, tools
+    for f in files:
         src = f.read_text()
         tree = ast.parse(src)  # syntax
         assert tree.body, f.name  # non-empty module
@@ -477,7 +483,7 @@ def test_bench_contract_cpu_smoke():
     out = subprocess.run(
         [sys.executable, "bench.py", "--steps", "2", "--warmup", "1",
          "--batch", "512", "--features", "16384", "--model", "fm"],
-        capture_output=True, text=True, timeout=300)
+        capture_output=True, text=True, timeout=300, cwd=_REPO_ROOT)
     assert out.returncode == 0, out.stderr[-800:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -488,3 +494,36 @@ def test_bench_contract_cpu_smoke():
         assert k in d, k
     assert d["steps"] == 2 and d["data"] == "synthetic"
     assert d["config"]["global_batch"] == 512
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's per-row loss as float
+    .npy, identically on a second run with the same arguments (seeded
+    inputs), and --full is accepted alongside it."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    got = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "3",
+             "--warmup", "1", "--batch", "256", "--features", "16384",
+             "--dump-outputs", str(d)] + extra,
+            capture_output=True, text=True, timeout=300, cwd=_REPO_ROOT)
+        assert out.returncode == 0, out.stderr[-800:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        res = json.loads(lines[0])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["loss.npy"], files
+        loss = np.load(d / "loss.npy")
+        assert loss.dtype in (np.float32, np.float64)
+        assert loss.shape == (256,) and np.isfinite(loss).all()
+        assert loss.nbytes <= 64 << 20
+        got.append(loss)
+    assert np.array_equal(got[0], got[1])

@@ -112,9 +112,12 @@ def test_proc_text_topic_tool(tmp_path):
     """Text prep parity with reference data/proc_text_topic.py: vocab by
     frequency (stopwords/markup dropped), dense count rows, and the
     sparse triples feed PLSAModel.fit directly."""
+    import os
     import subprocess
     import sys
 
+    tool = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
+                        "tools", "proc_text_topic.py")
     src = tmp_path / "corpus.txt"
     src.write_text(
         "<doc id=1>\n"
@@ -126,7 +129,7 @@ def test_proc_text_topic_tool(tmp_path):
     vocab = tmp_path / "vocab.txt"
     train = tmp_path / "train.csv"
     rc = subprocess.run(
-        [sys.executable, "tools/proc_text_topic.py", str(src), "10",
+        [sys.executable, tool, str(src), "10",
          "--vocab-out", str(vocab), "--train-out", str(train)],
         capture_output=True, text=True)
     assert rc.returncode == 0, rc.stderr
@@ -143,7 +146,7 @@ def test_proc_text_topic_tool(tmp_path):
     # sparse mode triples train PLSA end-to-end
     sp = tmp_path / "sparse.csv"
     rc = subprocess.run(
-        [sys.executable, "tools/proc_text_topic.py", str(src), "10",
+        [sys.executable, tool, str(src), "10",
          "--vocab-out", str(vocab), "--train-out", str(sp), "--sparse"],
         capture_output=True, text=True)
     assert rc.returncode == 0, rc.stderr
