@@ -222,6 +222,30 @@ class MLP:
         for la in self.layers:
             la.apply_grads()
 
+    # ---- flat views for parameter-server training: layer order, W then b
+    # per layer (the spec order of parallel.ps_dense.mlp_dense_spec) ----
+    def flat_params(self):
+        return torch.cat([t.reshape(-1) for la in self.layers
+                          for t in (la.W, la.b)])
+
+    def load_flat(self, flat):
+        want = sum(la.W.numel() + la.b.numel() for la in self.layers)
+        assert flat.numel() == want, \
+            f"flat has {flat.numel()} elements, the MLP needs {want}"
+        off = 0
+        for la in self.layers:
+            for p in (la.W, la.b):
+                p.copy_(flat[off:off + p.numel()].view_as(p))
+                off += p.numel()
+            if la._gpu:
+                la.Wbf.copy_(la.W.to(torch.bfloat16))
+                la.Wtbf.copy_(la.W.t().contiguous().to(torch.bfloat16))
+
+    def flat_grads(self):
+        """Gradients left in the layers by the last backward()."""
+        return torch.cat([t.reshape(-1) for la in self.layers
+                          for t in (la._dW, la._db)])
+
     def state_dict(self):
         return {f"layer{i}": la.state_dict()
                 for i, la in enumerate(self.layers)}

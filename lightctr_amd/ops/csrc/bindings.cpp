@@ -388,6 +388,94 @@ void ps_apply(at::Tensor lidx, at::Tensor gW, at::Tensor gV, at::Tensor W,
       (int)updater, (float)lr, (float)lam, (float)eps, cur_stream());
 }
 
+// ---- PS dense table (flat slab; payload fp32 | fp16 | uint8 codes) ----
+
+int dense_wire(const at::Tensor& payload,
+               const c10::optional<at::Tensor>& scale,
+               const c10::optional<at::Tensor>& table) {
+  CHK(payload.is_cuda() && payload.is_contiguous(),
+      "payload must be a contiguous GPU tensor");
+  if (payload.scalar_type() == at::kFloat) return 0;
+  if (payload.scalar_type() == at::kHalf) return 1;
+  CHK(payload.scalar_type() == at::kByte,
+      "payload must be fp32, fp16 or uint8 codes");
+  CHK(scale.has_value() && table.has_value(),
+      "uint8 codes need scale and table");
+  check_cuda_f32(*scale, "scale");
+  check_cuda_f32(*table, "table");
+  CHK(scale->numel() == 1, "scale must have 1 element");
+  CHK(table->numel() >= 1 && table->numel() <= 256,
+      "table must have 1..256 entries");
+  return 2;
+}
+
+void check_dense_flags(const at::Tensor& flags) {
+  check_cuda_i32(flags, "flags");
+  CHK(flags.numel() >= 2, "flags must hold {corrupt, dropped}");
+}
+
+void ps_dense_check(at::Tensor payload, c10::optional<at::Tensor> scale,
+                    c10::optional<at::Tensor> table, at::Tensor flags) {
+  const int wire = dense_wire(payload, scale, table);
+  check_dense_flags(flags);
+  lightctr::ps_dense_check_launch(
+      payload.data_ptr(), wire,
+      wire == 2 ? scale->data_ptr<float>() : nullptr,
+      wire == 2 ? table->data_ptr<float>() : nullptr,
+      wire == 2 ? (int)table->numel() : 0, payload.numel(),
+      flags.data_ptr<int>(), cur_stream());
+}
+
+void ps_dense_apply(at::Tensor payload, c10::optional<at::Tensor> scale,
+                    c10::optional<at::Tensor> table, at::Tensor slab,
+                    c10::optional<at::Tensor> acc,
+                    c10::optional<at::Tensor> shadow, at::Tensor flags,
+                    int64_t updater, double lr, double lam, double eps) {
+  const int wire = dense_wire(payload, scale, table);
+  check_dense_flags(flags);
+  check_cuda_f32(slab, "slab");
+  const long n = slab.numel();
+  CHK(payload.numel() == n, "payload and slab sizes differ");
+  CHK(updater >= 0 && updater <= 3, "updater must be 0..3");
+  const bool need_acc = updater == 1 || updater == 3;
+  const bool need_sh = updater == 2 || updater == 3;
+  CHK(acc.has_value() == need_acc, "acc is for adagrad/dcasgda only");
+  CHK(shadow.has_value() == need_sh, "shadow is for dcasgd/dcasgda only");
+  if (need_acc) {
+    check_cuda_f32(*acc, "acc");
+    CHK(acc->numel() == n, "acc and slab sizes differ");
+  }
+  if (need_sh) {
+    check_cuda_f32(*shadow, "shadow");
+    CHK(shadow->numel() == n, "shadow and slab sizes differ");
+  }
+  lightctr::ps_dense_apply_launch(
+      payload.data_ptr(), wire,
+      wire == 2 ? scale->data_ptr<float>() : nullptr,
+      wire == 2 ? table->data_ptr<float>() : nullptr,
+      wire == 2 ? (int)table->numel() : 0, slab.data_ptr<float>(),
+      need_acc ? acc->data_ptr<float>() : nullptr,
+      need_sh ? shadow->data_ptr<float>() : nullptr, n, (int)updater,
+      (float)lr, (float)lam, (float)eps, flags.data_ptr<int>(),
+      cur_stream());
+}
+
+at::Tensor ps_dense_pack(at::Tensor slab, c10::optional<at::Tensor> shadow,
+                         bool fp16) {
+  check_cuda_f32(slab, "slab");
+  const long n = slab.numel();
+  if (shadow) {
+    check_cuda_f32(*shadow, "shadow");
+    CHK(shadow->numel() == n, "shadow and slab sizes differ");
+  }
+  auto out = at::empty({n}, slab.options().dtype(fp16 ? at::kHalf
+                                                      : at::kFloat));
+  lightctr::ps_dense_pack_launch(
+      slab.data_ptr<float>(), out.data_ptr(), fp16 ? 1 : 0,
+      shadow ? shadow->data_ptr<float>() : nullptr, n, cur_stream());
+  return out;
+}
+
 // ---- generic sparse optimizers (D = latent block width, runtime) ----
 
 void sparse_adagrad_apply(at::Tensor uniq, at::Tensor count, at::Tensor W,
@@ -964,6 +1052,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Vh") = py::none());
   m.def("ps_apply", &ps_apply,
         "PS-side fused updater (sgd/adagrad/dcasgd/dcasgda)");
+  m.def("ps_dense_check", &ps_dense_check,
+        "PS dense push: non-finite scan of the payload -> flags[0]",
+        py::arg("payload"), py::arg("scale"), py::arg("table"),
+        py::arg("flags"));
+  m.def("ps_dense_apply", &ps_dense_apply,
+        "PS dense push: fused decode + updater over the slab, gated on "
+        "flags[0]; a gated push bumps flags[1]. flags[0] is only what the "
+        "last ps_dense_check left there: call ps_dense_check on the same "
+        "payload, on the same stream, immediately before every call (as "
+        "DenseTable.apply does) — called alone it acts on a stale flag",
+        py::arg("payload"), py::arg("scale"), py::arg("table"),
+        py::arg("slab"), py::arg("acc"), py::arg("shadow"),
+        py::arg("flags"), py::arg("updater"), py::arg("lr"),
+        py::arg("lam"), py::arg("eps"));
+  m.def("ps_dense_pack", &ps_dense_pack,
+        "PS dense pull: slab -> fp32/fp16 payload (+ shadow = slab)",
+        py::arg("slab"), py::arg("shadow"), py::arg("fp16"));
   m.def("sparse_ftrl_apply", &sparse_ftrl_apply,
         "generic sparse fused FTRL (runtime D; optional Adagrad on V)",
         py::arg("uniq"), py::arg("count"), py::arg("W"), py::arg("V"),

@@ -219,6 +219,19 @@ void lowbit_encode_launch(const float* x, unsigned int* words, float thresh,
 void lowbit_decode_launch(const unsigned int* words, float* x, float lo,
                           float hi, int bits, long n, ihipStream_t* stream);
 
+// --- ps_dense_kernels.hip (PS dense-table slab; wire 0=fp32 1=fp16 2=u8
+// codes; flags = {corrupt-push flag, dropped counter}) ---
+void ps_dense_check_launch(const void* payload, int wire, const float* scale,
+                           const float* table, int levels, long n,
+                           int* flags, ihipStream_t* stream);
+void ps_dense_apply_launch(const void* payload, int wire, const float* scale,
+                           const float* table, int levels, float* slab,
+                           float* acc, float* shadow, long n, int updater,
+                           float lr, float lam, float eps, int* flags,
+                           ihipStream_t* stream);
+void ps_dense_pack_launch(const float* slab, void* out, int fp16,
+                          float* shadow, long n, ihipStream_t* stream);
+
 // --- sort_kernels.hip ---
 void iota_i32_launch(int* out, int n, ihipStream_t* stream);
 unsigned long radix_sort_pairs_i32_temp_bytes(int n, int end_bit);

@@ -22,6 +22,14 @@ The PS applies per-key updates as requests arrive:
   * wire codec    — fp32, fp16 or int8-quantile payloads (reference's
                     varint/fp16/int8 compression, network.h +
                     quantile_compress.h), chosen per PSConfig.
+  * dense tables  — besides the sparse (W, V) rows each shard serves a
+                    contiguous range of one fused flat dense slab
+                    (PSConfig.dense_spec; ps_dense.DenseTable; reference
+                    tensorShardTable, paramserver.h:40-47) through
+                    OP_PULL_T / OP_PUSH_T: one request and one payload per
+                    shard per op, same SSP gate, stale-push drop, push
+                    lock and updaters as the sparse ops. ps_widedeep.py
+                    trains Wide&Deep through both tables.
 
 Transport is torch.distributed point-to-point (gloo on CPU tests; on the
 GPU node NCCL(=RCCL) send/recv over xGMI). The rendezvous that the
@@ -39,7 +47,10 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
+from .ps_dense import (DenseTable, dense_codec, dense_range, dense_total)
+
 OP_PULL, OP_PUSH, OP_FIN = 1, 2, 3
+OP_PULL_T, OP_PUSH_T = 4, 5  # dense-tensor table ops (reference 'T' msgs)
 FLAG_RETRY = 1
 
 
@@ -56,6 +67,10 @@ class PSConfig:
     wire: str = "fp32"  # fp32 | fp16 | int8
     init_sigma: float = 0.01
     seed: int = 1234
+    # dense-tensor table: ordered ((name, shape), ...) fused into one flat
+    # slab split over the shards by dense_range(); () = no dense table
+    dense_spec: tuple = ()
+    dense_int8_mode: str = "log"  # codec table for dense int8 pushes
 
 
 def _owner(fids: torch.Tensor, ps_shards: int) -> torch.Tensor:
@@ -79,12 +94,30 @@ def setup_pair_groups(cfg: "PSConfig"):
 class PSShard:
     """Server loop for one parameter-shard rank."""
 
-    def __init__(self, cfg: PSConfig, device: str = "cpu"):
+    def __init__(self, cfg: PSConfig, device: str = "cpu", dense_init=None):
+        """dense_init: optional flat tensor [dense_total(cfg.dense_spec)]
+        with the initial dense slab (every shard takes its own range)."""
         self.cfg = cfg
         self.device = torch.device(device)
         self.rank = dist.get_rank()
         self.world = dist.get_world_size()
         self.n_workers = self.world - cfg.ps_shards
+        self.dense = None
+        total = dense_total(cfg.dense_spec)
+        self.dense_lo, self.dense_hi = dense_range(total, cfg.ps_shards,
+                                                   self.rank)
+        if self.dense_hi > self.dense_lo:
+            if dense_init is not None:
+                assert dense_init.numel() == total
+                dense_init = dense_init.reshape(-1)[
+                    self.dense_lo:self.dense_hi]
+            self.dense = DenseTable(
+                self.dense_hi - self.dense_lo, updater=cfg.updater,
+                lr=cfg.lr, dc_lambda=cfg.dc_lambda, eps=cfg.eps,
+                n_workers=self.n_workers, device=device, init=dense_init,
+                init_sigma=cfg.init_sigma,
+                seed=cfg.seed + 31 * self.rank + 17,
+                int8_mode=cfg.dense_int8_mode)
         F = (cfg.num_features + cfg.ps_shards - 1) // cfg.ps_shards
         self.F_local = F
         g = torch.Generator().manual_seed(cfg.seed + 31 * self.rank)
@@ -120,7 +153,9 @@ class PSShard:
         paramserver.h:138-139: a pull may observe a value mid-update —
         async-SGD semantics absorb it); only pushes serialize against
         each other under a lock so concurrent same-key updates do not
-        interleave their read-modify-writes. Returns when all workers
+        interleave their read-modify-writes. A Hogwild pull may therefore
+        observe TORN values (rows or a dense slab partly updated by a
+        concurrent push), not only stale ones. Returns when all workers
         FIN."""
         cfg = self.cfg
         self._lock = threading.Lock()
@@ -146,19 +181,35 @@ class PSShard:
                 self._handle_pull(w, wi, epoch, n, group)
             elif op == OP_PUSH:
                 self._handle_push(w, wi, epoch, n, flags, group)
+            elif op == OP_PULL_T:
+                self._handle_pull_t(w, wi, epoch, n, group)
+            elif op == OP_PUSH_T:
+                self._handle_push_t(w, wi, epoch, n, flags, group)
+
+    def _ssp_admit(self, w, wi, epoch, group) -> bool:
+        """SSP pull gate shared by the sparse and dense pulls: record the
+        worker's clock, send the reply header, and return False when the
+        pull was refused (worker retries)."""
+        self.worker_epoch[wi] = epoch
+        fastest_allowed = int(self.worker_epoch[
+            self.worker_epoch >= 0].min()) + self.cfg.staleness
+        reply = torch.zeros(4, dtype=torch.long, device=self.device)
+        admitted = epoch <= fastest_allowed
+        if not admitted:
+            reply[3] = FLAG_RETRY  # SSP gate: refuse, worker retries
+        dist.send(reply, dst=w, group=group)
+        return admitted
+
+    def _push_is_stale(self, epoch) -> bool:
+        """stale-push drop (reference paramserver.h:199-208), shared by the
+        sparse and dense pushes."""
+        return epoch + self.cfg.staleness < int(self.worker_epoch.max())
 
     def _handle_pull(self, w, wi, epoch, n, group):
         cfg = self.cfg
         fids = self._recv((n,), torch.long, w, group)
-        self.worker_epoch[wi] = epoch
-        fastest_allowed = int(self.worker_epoch[
-            self.worker_epoch >= 0].min()) + cfg.staleness
-        reply = torch.zeros(4, dtype=torch.long, device=self.device)
-        if epoch > fastest_allowed:
-            reply[3] = FLAG_RETRY  # SSP gate: refuse, worker retries
-            dist.send(reply, dst=w, group=group)
+        if not self._ssp_admit(w, wi, epoch, group):
             return
-        dist.send(reply, dst=w, group=group)
         lidx = fids // cfg.ps_shards
         # Hogwild read — no lock (see serve() docstring). The shadow
         # copies are per-worker slices written only by this worker's
@@ -194,12 +245,42 @@ class PSShard:
         # wire validity check (reference paramserver.h:172,244)
         if not bool(torch.isfinite(gW).all() and torch.isfinite(gV).all()):
             return  # drop corrupt push rather than poison the table
-        # stale-push drop (reference paramserver.h:199-208)
-        if epoch + cfg.staleness < int(self.worker_epoch.max()):
+        if self._push_is_stale(epoch):
             return
         lidx = fids // cfg.ps_shards
         with self._lock:
             self._apply(wi, lidx, gW, gV)
+
+    def _handle_pull_t(self, w, wi, epoch, n, group):
+        """Dense pull: the whole shard range in one payload message."""
+        assert self.dense is not None and n == self.dense.n
+        if not self._ssp_admit(w, wi, epoch, group):
+            return
+        # Hogwild read, like the sparse pull; shadow[wi] is written only
+        # by this worker's serving thread
+        dist.send(self.dense.pack(wi, self.cfg.wire), dst=w, group=group)
+
+    def _handle_push_t(self, w, wi, epoch, n, flags, group):
+        """Dense push: one payload message for the whole shard range (+ a
+        1-element scale for int8). Corrupt pushes are dropped inside
+        DenseTable.apply (counted in dense.dropped)."""
+        cfg = self.cfg
+        assert self.dense is not None and n == self.dense.n
+        scale = None
+        if cfg.wire == "int8" and flags == 1:
+            scale = self._recv((1,), torch.float32, w, group)
+            payload = self._recv((n,), torch.uint8, w, group)
+            wire = "int8"
+        elif cfg.wire == "fp16":
+            payload = self._recv((n,), torch.float16, w, group)
+            wire = "fp16"
+        else:
+            payload = self._recv((n,), torch.float32, w, group)
+            wire = "fp32"
+        if self._push_is_stale(epoch):
+            return
+        with self._lock:
+            self.dense.apply(wi, payload, wire, scale)
 
     def _apply(self, wi, lidx, gW, gV):
         cfg = self.cfg
@@ -259,6 +340,25 @@ class PSWorker:
             from ..utils.compress import QuantileCodec
 
             self._codec = QuantileCodec(mode="log", device=device)
+        self._dense_total = dense_total(cfg.dense_spec)
+        self._dense_codec = None
+        if cfg.wire == "int8" and self._dense_total > 0:
+            self._dense_codec = dense_codec(cfg.dense_int8_mode, device)
+
+    def _pull_request(self, ps, op, epoch, n, body=None):
+        """Send a pull request (header + optional body) to shard ps until
+        the SSP gate admits it (50 ms retry, like pull.h:63-67)."""
+        while True:
+            hdr = torch.tensor([op, epoch, n, 0], dtype=torch.long,
+                               device=self.device)
+            dist.send(hdr, dst=ps, group=self.group)
+            if body is not None:
+                dist.send(body, dst=ps, group=self.group)
+            reply = torch.zeros(4, dtype=torch.long, device=self.device)
+            dist.recv(reply, src=ps, group=self.group)
+            if int(reply[3]) != FLAG_RETRY:
+                return
+            time.sleep(0.05)
 
     def pull(self, fids_uniq: torch.Tensor, epoch: int):
         """fids_uniq: int64 sorted unique. Returns (W[U], V[U,K]) in the
@@ -272,16 +372,7 @@ class PSWorker:
             f = fids_uniq[sel]
             if f.numel() == 0:
                 continue
-            while True:
-                hdr = torch.tensor([OP_PULL, epoch, f.numel(), 0],
-                                   dtype=torch.long, device=self.device)
-                dist.send(hdr, dst=ps, group=self.group)
-                dist.send(f, dst=ps, group=self.group)
-                reply = torch.zeros(4, dtype=torch.long, device=self.device)
-                dist.recv(reply, src=ps, group=self.group)
-                if int(reply[3]) != FLAG_RETRY:
-                    break
-                time.sleep(0.05)
+            self._pull_request(ps, OP_PULL, epoch, f.numel(), f)
             if cfg.wire == "fp16":
                 Wv = torch.empty(f.numel(), dtype=torch.float16,
                                  device=self.device)
@@ -343,6 +434,51 @@ class PSWorker:
             else:
                 dist.send(gW[sel].contiguous(), dst=ps, group=self.group)
                 dist.send(gV[sel].contiguous(), dst=ps, group=self.group)
+
+    def _dense_ranges(self):
+        """(shard, lo, hi) of every non-empty dense shard range."""
+        for ps in range(self.cfg.ps_shards):
+            lo, hi = dense_range(self._dense_total, self.cfg.ps_shards, ps)
+            if hi > lo:
+                yield ps, lo, hi
+
+    def pull_dense(self, epoch: int) -> torch.Tensor:
+        """The whole fused dense slab as flat fp32 [total] (spec order):
+        one request + one payload message per non-empty shard."""
+        out = torch.empty(self._dense_total, device=self.device)
+        dt = torch.float16 if self.cfg.wire == "fp16" else torch.float32
+        for ps, lo, hi in self._dense_ranges():
+            self._pull_request(ps, OP_PULL_T, epoch, hi - lo)
+            buf = torch.empty(hi - lo, dtype=dt, device=self.device)
+            dist.recv(buf, src=ps, group=self.group)
+            out[lo:hi] = buf
+        return out
+
+    def push_dense(self, flat_grad: torch.Tensor, epoch: int):
+        """Push the flat dense gradient [total]. A gradient with any
+        non-finite value is dropped locally (whole push); there is no
+        per-key magnitude filter on the dense path."""
+        cfg = self.cfg
+        assert flat_grad.numel() == self._dense_total
+        flat_grad = flat_grad.reshape(-1)
+        if not bool(torch.isfinite(flat_grad).all()):
+            return
+        use_int8 = cfg.wire == "int8"
+        for ps, lo, hi in self._dense_ranges():
+            g = flat_grad[lo:hi]
+            hdr = torch.tensor([OP_PUSH_T, epoch, hi - lo,
+                                1 if use_int8 else 0],
+                               dtype=torch.long, device=self.device)
+            dist.send(hdr, dst=ps, group=self.group)
+            if use_int8:
+                scale = g.abs().max().reshape(1).clamp(min=1e-12)
+                dist.send(scale, dst=ps, group=self.group)
+                dist.send(self._dense_codec.encode(g / scale), dst=ps,
+                          group=self.group)
+            elif cfg.wire == "fp16":
+                dist.send(g.to(torch.float16), dst=ps, group=self.group)
+            else:
+                dist.send(g.contiguous(), dst=ps, group=self.group)
 
     def fin(self):
         for ps in range(self.cfg.ps_shards):

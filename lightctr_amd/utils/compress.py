@@ -40,10 +40,16 @@ def _normal_cdf_inv(p: torch.Tensor) -> torch.Tensor:
 
 
 class QuantileCodec:
-    """Table-based scalar quantizer. mode: uniform | log | normal."""
+    """Table-based scalar quantizer. mode: uniform | log | normal | custom.
+
+    mode="custom" places the levels at equal steps of the CDF of
+    N(mu, sigma) between lo and hi (reference CUSTOM_DISTRIBUT,
+    quantile_compress.h:101-106) — for near-normal values such as dense MLP
+    gradients. from_table() wraps a caller-supplied table."""
 
     def __init__(self, levels: int = 256, mode: str = "uniform",
-                 lo: float = -1.0, hi: float = 1.0, device: str = "cpu"):
+                 lo: float = -1.0, hi: float = 1.0, device: str = "cpu",
+                 mu: float = 0.0, sigma: float = 1.0):
         assert levels <= 256
         self.levels = levels
         p = (torch.arange(levels, dtype=torch.float64) + 0.5) / levels
@@ -57,9 +63,31 @@ class QuantileCodec:
             t = torch.sort(t).values
         elif mode == "normal":
             t = _normal_cdf_inv(p) * (hi - lo) / 6.0 + (hi + lo) / 2.0
+        elif mode == "custom":
+            assert sigma > 0 and hi > lo
+            sd = math.sqrt(2.0) * sigma
+            ends = torch.erf((torch.tensor([lo, hi], dtype=torch.float64)
+                              - mu) / sd)
+            c_lo, c_hi = 0.5 * (1 + ends[0]), 0.5 * (1 + ends[1])
+            assert c_hi > c_lo, "no normal mass between lo and hi"
+            t = mu + sigma * _normal_cdf_inv(c_lo + (c_hi - c_lo) * p)
+            t = t.clamp(lo, hi)
         else:
             raise ValueError(mode)
         self.table = t.float().to(device)
+
+    @classmethod
+    def from_table(cls, sorted_table, device: str = "cpu"):
+        """Codec over a caller-supplied table: 1-D, finite, strictly
+        increasing, at most 256 entries."""
+        t = torch.as_tensor(sorted_table, dtype=torch.float32).reshape(-1)
+        assert 1 <= t.numel() <= 256
+        assert bool(torch.isfinite(t).all())
+        assert bool((t[1:] > t[:-1]).all()), "table must strictly increase"
+        c = cls.__new__(cls)
+        c.levels = t.numel()
+        c.table = t.clone().to(device)
+        return c
 
     def encode(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda:
