@@ -8,6 +8,8 @@ command:
     python -m lightctr_amd.cli train --model fm --data path.csv --epochs 5
     python -m lightctr_amd.cli train --model ffm|nfm|widedeep|gbm ...
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
+    python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
+        --data dense.csv ...      (dense rows; served by the compiled forest)
 
 Distributed modes are launched via torch.distributed.run (one rank per
 GPU), selecting --mode ring|sharded|ps at runtime.
@@ -43,6 +45,9 @@ def _load_data(args):
 
 def cmd_train(args) -> int:
     dev = _device(args)
+    if args.model not in ("fm", "ffm", "nfm", "widedeep", "lr"):
+        # the rest of the zoo reads dense / text data, not libffm
+        return _train_other(args, dev)
     ds = _load_data(args)
     F = max(args.features, ds.num_features)
     if args.model == "fm":
@@ -138,6 +143,16 @@ def _dense_data(args):
     return load_dense_csv(args.data, max_rows=args.rows or None)
 
 
+def _binary_labels(y):
+    """gbdt_lr is a binary model: a multi-class label column is read as
+    class 0 against the rest."""
+    if int(y.max()) > 1:
+        print("gbdt_lr: labels binarised as (label > 0)", file=sys.stderr,
+              flush=True)
+        return (y > 0).long()
+    return y
+
+
 def _train_other(args, dev) -> int:
     """The rest of the zoo (reference main.cpp TEST_* coverage): gbm, cnn,
     rnn, vae, gmm, embed, plsa."""
@@ -163,6 +178,25 @@ def _train_other(args, dev) -> int:
         else:
             acc = float((p.argmax(dim=1).cpu() == y).float().mean())
             print(json.dumps({"final": {"accuracy": acc}}))
+        if args.save:
+            m.save(args.save)
+        return 0
+    if args.model == "gbdt_lr":
+        from .models.gbdt_lr import GBDTLRHyper, GBDTLRModel
+        from .models.gbm import GBMHyper
+        from .utils.metrics import auc_score
+
+        X, y = _dense_data(args)
+        y = _binary_labels(y)
+        m = GBDTLRModel(GBDTLRHyper(
+            gbm=GBMHyper(n_rounds=args.epochs * 5, max_depth=5, n_classes=2,
+                         seed=args.seed),
+            lr_optimizer=args.optimizer, lr_lr=args.lr, epochs=args.epochs,
+            batch=args.batch, seed=args.seed), device=dev)
+        m.fit(X.to(dev), y.float().to(dev),
+              log=lambda msg: print(msg, flush=True))
+        p = m.predict_proba(X.to(dev))
+        print(json.dumps({"final": {"auc": auc_score(p.cpu(), y.float())}}))
         if args.save:
             m.save(args.save)
         return 0
@@ -308,8 +342,43 @@ def _train_other(args, dev) -> int:
     return 2
 
 
+def _predict_dense(args, dev) -> int:
+    """gbm / gbdt_lr serving: dense rows through the compiled forest."""
+    from .predict.predictor import BatchPredictor
+
+    if not args.load:
+        print(f"predict --model {args.model} needs --load", file=sys.stderr)
+        return 2
+    X, y = _dense_data(args)
+    if args.model == "gbm":
+        from .predict.forest import CompiledForest
+
+        model = CompiledForest.load(args.load, dev)
+    else:
+        from .models.gbdt_lr import GBDTLRHyper, GBDTLRModel
+
+        model = GBDTLRModel(GBDTLRHyper(), device=dev)
+        model.load(args.load)
+        y = _binary_labels(y)
+    bp = BatchPredictor(model, batch_size=args.batch)
+    pred = bp.predict_dense(X.to(dev))
+    if pred.dim() == 1:
+        rep = bp.report(pred, y.float().to(dev), dump_path=args.dump)
+    else:  # softmax forest: accuracy, and one row of class scores each
+        rep = {"accuracy": float((pred.argmax(dim=1).cpu() == y)
+                                 .float().mean())}
+        if args.dump:
+            with open(args.dump, "w") as f:
+                for row in pred.cpu().tolist():
+                    f.write(" ".join(f"{v:.6f}" for v in row) + "\n")
+    print(json.dumps(rep))
+    return 0
+
+
 def cmd_predict(args) -> int:
     dev = _device(args)
+    if args.model in ("gbm", "gbdt_lr"):
+        return _predict_dense(args, dev)
     ds = _load_data(args).to(torch.device(dev))
     F = max(args.features, ds.num_features)
     if args.model == "fm":

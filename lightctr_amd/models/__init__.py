@@ -11,6 +11,7 @@ from .vae import VAEModel, VAEHyper
 from .cnn import CNNModel, CNNHyper, Conv2DLayer, MaxPool2DLayer
 from .rnn import RNNModel, RNNHyper, LSTMUnit, AttentionUnit
 from .lr import LRModel, LRHyper, LRTrainer
+from .gbdt_lr import GBDTLRModel, GBDTLRHyper
 
 __all__ = [
     "FMModel", "FMTrainer", "FMHyper",
@@ -26,4 +27,5 @@ __all__ = [
     "CNNModel", "CNNHyper", "Conv2DLayer", "MaxPool2DLayer",
     "RNNModel", "RNNHyper", "LSTMUnit", "AttentionUnit",
     "LRModel", "LRHyper", "LRTrainer",
+    "GBDTLRModel", "GBDTLRHyper",
 ]

@@ -307,6 +307,12 @@ class GBMModel:
             return torch.sigmoid(m[:, 0])
         return torch.softmax(m, dim=1)
 
+    def compile(self, device=None):
+        """Pack the forest for fused inference (predict.CompiledForest)."""
+        from ..predict.forest import CompiledForest
+
+        return CompiledForest.from_model(self, device=device)
+
     # ---- checkpoint (reference saveModel is a stub; ours is real) ----
     def save(self, path: str):
         torch.save({"hyper": self.h.__dict__,

@@ -989,6 +989,47 @@ at::Tensor gbm_hist(at::Tensor bins, at::Tensor grad, at::Tensor hess,
   return hist;
 }
 
+// Compiled-forest inference (predict/forest.py). The tables come from
+// CompiledForest, which validates the trees; shapes are re-checked here.
+at::Tensor gbm_forest(at::Tensor X, at::Tensor nodes, at::Tensor tree_off,
+                      at::Tensor tree_class, at::Tensor leaf_base,
+                      at::Tensor chunks, int64_t mode, int64_t n_features,
+                      int64_t n_classes, int64_t max_depth,
+                      int64_t fid_offset) {
+  check_cuda_f32(X, "X");
+  CHK(X.dim() == 2 && X.size(1) == n_features, "X must be [N, ",
+      n_features, "]");
+  check_cuda_i32(nodes, "nodes");
+  check_cuda_i32(tree_off, "tree_off");
+  check_cuda_i32(tree_class, "tree_class");
+  check_cuda_i32(leaf_base, "leaf_base");
+  check_cuda_i32(chunks, "chunks");
+  CHK(nodes.dim() == 2 && nodes.size(1) == 4, "nodes must be [n, 4]");
+  CHK(chunks.dim() == 2 && chunks.size(1) == 4, "chunks must be [c, 4]");
+  CHK(((uintptr_t)nodes.data_ptr()) % 16 == 0 &&
+          ((uintptr_t)chunks.data_ptr()) % 16 == 0,
+      "nodes/chunks must be 16-byte aligned");
+  CHK(mode >= 0 && mode <= 2, "mode must be 0 (margin), 1 (leaf), 2 (fid)");
+  CHK(n_classes >= 1 && max_depth >= 0, "bad n_classes / max_depth");
+  const int64_t N = X.size(0), T = tree_class.numel();
+  CHK(tree_off.numel() == T + 1 && leaf_base.numel() == T,
+      "tree tables disagree on the tree count");
+  CHK(n_features >= 1 || N == 0, "X needs at least one column");
+  CHK(N * std::max<int64_t>(T, n_classes) < ((int64_t)1 << 40),
+      "output too large");
+  at::Tensor out =
+      mode == 0 ? at::zeros({N, n_classes}, X.options())
+                : at::empty({N, T}, X.options().dtype(at::kInt));
+  if (N == 0 || T == 0 || chunks.size(0) == 0) return out;
+  lightctr::gbm_forest_launch(
+      X.data_ptr<float>(), nodes.data_ptr(), tree_off.data_ptr<int>(),
+      tree_class.data_ptr<int>(), leaf_base.data_ptr<int>(),
+      chunks.data_ptr(), (int)chunks.size(0), out.data_ptr(), (long)N,
+      (int)n_features, (int)T, (int)n_classes, (int)max_depth,
+      (int)fid_offset, (int)mode, cur_stream());
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1101,6 +1142,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lowbit_encode", &lowbit_encode, "1/2-bit sign quantize");
   m.def("lowbit_decode", &lowbit_decode, "1/2-bit dequantize");
   m.def("gbm_hist", &gbm_hist, "GBM per-node (grad,hess) histograms");
+  m.def("gbm_forest", &gbm_forest,
+        "compiled-forest inference: margin / leaf id / leaf feature id");
+  m.def("gbm_forest_chunk_capacity", &lightctr::gbm_forest_chunk_capacity,
+        "nodes per LDS chunk of the forest kernel");
+  m.def("gbm_forest_max_register_classes",
+        &lightctr::gbm_forest_max_register_classes,
+        "largest class count with register accumulators");
+  m.def("gbm_forest_rows_per_grid", &lightctr::gbm_forest_rows_per_grid,
+        "rows one trip of the clamped grid covers");
   m.def("nfm_forward", &nfm_forward,
         "NFM bi-interaction fwd (wide, sumVX, vec, vec_bf16)");
   m.def("nfm_backward_emit", &nfm_backward_emit,

@@ -244,5 +244,15 @@ void radix_sort_pairs_i32_launch(void* temp, unsigned long temp_bytes,
 void gbm_hist_launch(const unsigned char* bins, const float* grad,
                      const float* hess, const int* node_of_row, float* hist,
                      int N, int D, int n_nodes, ihipStream_t* stream);
+// compiled-forest inference; mode 0 = margin (out fp32 [N,K]), 1 = leaf id,
+// 2 = leaf feature id (out int32 [N,T]); nodes/chunks are 16-byte records
+int gbm_forest_chunk_capacity();
+int gbm_forest_max_register_classes();
+long gbm_forest_rows_per_grid();
+void gbm_forest_launch(const float* X, const void* nodes, const int* tree_off,
+                       const int* tree_class, const int* leaf_base,
+                       const void* chunks, int n_chunks, void* out, long N,
+                       int D, int T, int K, int max_depth, int fid_offset,
+                       int mode, ihipStream_t* stream);
 
 }  // namespace lightctr

@@ -32,6 +32,16 @@ class BatchPredictor:
             out.append(p)
         return torch.cat(out)
 
+    def predict_dense(self, X: torch.Tensor) -> torch.Tensor:
+        """X: dense [N, D] rows for models whose predict_proba takes a
+        tensor (CompiledForest, GBMModel, GBDTLRModel)."""
+        out = []
+        for s in range(0, X.shape[0], self.batch_size):
+            out.append(self.model.predict_proba(X[s:s + self.batch_size]))
+        if not out:
+            return self.model.predict_proba(X)
+        return torch.cat(out)
+
     def report(self, pred: torch.Tensor, labels: torch.Tensor,
                dump_path: str | None = None) -> dict:
         p = pred.clamp(1e-7, 1 - 1e-7)
