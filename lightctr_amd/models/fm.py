@@ -6,8 +6,11 @@ Capability parity with the reference Train_FM_Algo
 Adagrad apply) — rebuilt GPU-first:
 
   * parameters W [F] and V [F,K] are flat fp32 slabs resident in HBM3E
-  * the train step is 5 HIP kernel launches (forward, loss, backward-scatter,
-    bitmap-compact, fused sparse optimizer) with no device->host syncs
+  * the train step is a handful of HIP kernel launches with no device->host
+    syncs: forward, loss, per-entry gradient emit, radix sort, then (default
+    backward_mode="segment") a work-list pass and a per-piece segment reduce
+    with the optimizer fused in; "sorted" (walk into slabs + bitmap compact
+    + sparse optimizer) and "atomic" (scatter backward) stay selectable
   * CPU path uses the fp32 torch reference ops (same math; the test oracle)
   * optimizers: adagrad (reference default) and FTRL-proximal (BASELINE
     config #2: "FM k=16 ... FTRL fused update"); both are applied only to
@@ -75,7 +78,14 @@ class FMModel:
         self.uniq = torch.zeros(cap, dtype=torch.int32, device=self.device)
         self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._use_hip = self.device.type == "cuda"
-        self.backward_mode = "sorted"  # "sorted" (default) | "atomic"
+        # "segment" (default) | "sorted" | "atomic"
+        # segment: sort, then one K-lane subgroup per piece (a run of equal
+        # fids cut at multiples of segment_cap) sums its gradients and, for
+        # a run that fits one piece, applies the optimizer in place; only
+        # runs crossing a cut go through the slabs + the sparse apply, with
+        # uniq/count as their spill list. No bitmap pass in this mode.
+        self.backward_mode = "segment"
+        self.segment_cap = 256  # power of two; sweep in docs/KERNELS.md
         # fused-apply: interior feature segments get their optimizer update
         # inside the segment-reduce kernel. Measured NET-NEGATIVE in both
         # rounds (round 1: optimizer RMWs serialize the segment walk,
@@ -113,7 +123,13 @@ class FMModel:
             ops = require_hip_ops()
             pred, sumVX = ops.fm_forward(row_ptr, fids, vals, self.W, self.V)
             loss, dpred = ops.logloss_grad(pred, labels, scale)
-            if self.backward_mode == "sorted":
+            # fused_apply is a variant of the walk: asking for it selects
+            # the sorted path
+            if self.backward_mode == "segment" and not self.fused_apply:
+                self._segment_backward(ops, row_ptr, fids, vals, sumVX,
+                                       dpred)
+                return loss
+            if self.backward_mode in ("sorted", "segment"):
                 # contention-free backward: emit per-entry grads
                 # (coalesced), bit-range radix-sort the fids, then
                 # segment-reduce into the slabs with interior-store
@@ -161,18 +177,7 @@ class FMModel:
             self.count.zero_()
             ops.bitmap_compact(self.touched, self.uniq, self.count)
             live = self.uniq[: min(self.uniq.numel(), fids.numel())]
-            if self.h.optimizer == "ftrl":
-                ops.fm_ftrl_apply(live, self.count, self.W, self.V,
-                                  self.zW, self.nW, self.zV, self.nV,
-                                  self.gradW, self.gradV, self.h.ftrl_alpha,
-                                  self.h.ftrl_beta, self.h.ftrl_l1,
-                                  self.h.ftrl_l2,
-                                  1 if self.h.ftrl_v == "adagrad" else 0,
-                                  self.h.lr, self.h.eps, self.h.l2)
-            else:
-                ops.fm_adagrad_apply(live, self.count, self.W, self.V,
-                                     self.nW, self.nV, self.gradW, self.gradV,
-                                     self.h.lr, self.h.eps, self.h.l2)
+            self._sparse_apply(ops, live)
             return loss
         # CPU reference path
         pred, sumVX = fm_ref.fm_forward_ref(row_ptr, fids, vals, self.W, self.V)
@@ -194,6 +199,55 @@ class FMModel:
                                      self.gradW, self.gradV, self.h.lr,
                                      self.h.eps, self.h.l2)
         return loss
+
+    def _opt_mode(self) -> int:
+        """Kernel-side optimizer pairing: 1 Adagrad, 2 FTRL, 3 FTRL-W +
+        Adagrad-V."""
+        if self.h.optimizer != "ftrl":
+            return 1
+        return 3 if self.h.ftrl_v == "adagrad" else 2
+
+    def _sparse_apply(self, ops, live):
+        """Optimizer over the fid list live[:count]; re-zeroes the slab
+        entries it consumes."""
+        if self.h.optimizer == "ftrl":
+            ops.fm_ftrl_apply(live, self.count, self.W, self.V,
+                              self.zW, self.nW, self.zV, self.nV,
+                              self.gradW, self.gradV, self.h.ftrl_alpha,
+                              self.h.ftrl_beta, self.h.ftrl_l1,
+                              self.h.ftrl_l2,
+                              1 if self.h.ftrl_v == "adagrad" else 0,
+                              self.h.lr, self.h.eps, self.h.l2)
+        else:
+            ops.fm_adagrad_apply(live, self.count, self.W, self.V,
+                                 self.nW, self.nV, self.gradW, self.gradV,
+                                 self.h.lr, self.h.eps, self.h.l2)
+
+    def _segment_backward(self, ops, row_ptr, fids, vals, sumVX, dpred):
+        nnz = fids.numel()
+        if nnz == 0:
+            return
+        cap = int(self.segment_cap)
+        sorted_fids, perm = sort_ids(fids, self.h.num_features)
+        gw, gv = ops.fm_backward_emit(row_ptr, fids, vals, self.V, sumVX,
+                                      dpred)
+        # the work-list pass also resets the spill counter
+        piece_start, n_pieces = ops.segment_worklist(sorted_fids, cap,
+                                                     self.count)
+        # a spilled run crosses a multiple of cap, and is a distinct fid
+        spill = self.uniq[: min(self.uniq.numel(), nnz // cap + 1)]
+        mode = self._opt_mode()
+        if mode == 1:
+            knobs = (self.h.lr, self.h.eps, self.h.l2, 0.0)
+        else:
+            knobs = (self.h.ftrl_alpha, self.h.ftrl_beta, self.h.ftrl_l1,
+                     self.h.ftrl_l2)
+        ops.fm_segment_apply(
+            sorted_fids, perm, piece_start, n_pieces, gw, gv, self.gradW,
+            self.gradV, spill, self.count, self.W, self.V, self.nW, self.nV,
+            self.zW if mode != 1 else None, self.zV if mode == 2 else None,
+            mode, *knobs, v_lr=self.h.lr, v_eps=self.h.eps, v_l2=self.h.l2)
+        self._sparse_apply(ops, spill)
 
     # -- checkpoint (reference saveModel/loadModel, fm_algo_abst.h:109-135) --
     def state_dict(self) -> dict:

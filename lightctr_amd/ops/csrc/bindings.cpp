@@ -189,6 +189,107 @@ void fm_sorted_apply_fused(at::Tensor sorted_fids,
       (float)v_l2, 384, cur_stream());
 }
 
+// Work list of the segment backward: (piece_start int32 [nnz], n_pieces
+// int32 [1]); the first n_pieces entries of piece_start are the piece
+// starts in order. Temp storage comes from the torch allocator, no host
+// sync. `reset` (optional int32 [1]) is zeroed by the same pass.
+std::vector<at::Tensor> segment_worklist(at::Tensor sorted_fids, int64_t cap,
+                                         c10::optional<at::Tensor> reset) {
+  check_cuda_i32(sorted_fids, "sorted_fids");
+  CHK(cap >= 1 && cap <= (1 << 30) && (cap & (cap - 1)) == 0,
+      "cap must be a power of two");
+  const int n = (int)sorted_fids.numel();
+  auto piece_start = at::empty({n}, sorted_fids.options());
+  int* reset_ptr = nullptr;
+  if (reset.has_value()) {
+    check_cuda_i32(*reset, "reset");
+    CHK(reset->numel() >= 1, "reset must hold one int");
+    reset_ptr = reset->data_ptr<int>();
+  }
+  if (n == 0) {
+    if (reset.has_value()) reset->zero_();
+    return {piece_start, at::zeros({1}, sorted_fids.options())};
+  }
+  auto n_pieces = at::empty({1}, sorted_fids.options());
+  const unsigned long bytes = lightctr::segment_worklist_temp_bytes(n);
+  auto temp = at::empty({(long)bytes}, sorted_fids.options().dtype(at::kByte));
+  lightctr::segment_worklist_launch(
+      temp.data_ptr(), bytes, sorted_fids.data_ptr<int>(), n, (int)cap,
+      piece_start.data_ptr<int>(), n_pieces.data_ptr<int>(), reset_ptr,
+      cur_stream());
+  return {piece_start, n_pieces};
+}
+
+// Segment backward: one K-lane subgroup per piece of the work list sums the
+// piece's gradients; whole pieces get the optimizer update in place,
+// partial ones go to the slabs and `spill` (fid list + counter, consumed by
+// fm_adagrad_apply / fm_ftrl_apply). opt_mode as in fm_sorted_apply_fused.
+void fm_segment_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
+                      at::Tensor piece_start, at::Tensor n_pieces,
+                      at::Tensor gw, at::Tensor gv, at::Tensor gradW,
+                      at::Tensor gradV, at::Tensor spill,
+                      at::Tensor spill_count, at::Tensor W, at::Tensor V,
+                      at::Tensor nW, at::Tensor nV,
+                      c10::optional<at::Tensor> zW,
+                      c10::optional<at::Tensor> zV, int64_t opt_mode,
+                      double p0, double p1, double p2, double p3, double v_lr,
+                      double v_eps, double v_l2) {
+  check_cuda_i32(sorted_fids, "sorted_fids");
+  check_cuda_i32(piece_start, "piece_start");
+  check_cuda_i32(n_pieces, "n_pieces");
+  check_cuda_i32(spill, "spill");
+  check_cuda_i32(spill_count, "spill_count");
+  check_cuda_f32(gw, "gw");
+  check_cuda_f32(gv, "gv");
+  check_cuda_f32(gradW, "gradW");
+  check_cuda_f32(gradV, "gradV");
+  check_cuda_f32(W, "W");
+  check_cuda_f32(V, "V");
+  check_cuda_f32(nW, "nW");
+  check_cuda_f32(nV, "nV");
+  const long nnz = sorted_fids.numel();
+  const int K = (int)V.size(1);
+  CHK(piece_start.numel() >= nnz, "piece_start must hold nnz entries");
+  CHK(n_pieces.numel() >= 1 && spill_count.numel() >= 1, "counters");
+  CHK(gw.numel() == nnz && gv.numel() == nnz * K, "gw/gv shape");
+  CHK(gradV.numel() == V.numel() && gradW.numel() == W.numel() &&
+          nV.numel() == V.numel() && nW.numel() == W.numel() &&
+          V.numel() == W.numel() * K,
+      "parameter / state / slab shapes must match");
+  CHK(opt_mode == 1 || opt_mode == 2 || opt_mode == 3,
+      "opt_mode 1=adagrad 2=ftrl 3=ftrlW+adagradV");
+  if (opt_mode != 1) {
+    CHK(zW.has_value(), "FTRL needs zW");
+    check_cuda_f32(*zW, "zW");
+    CHK(zW->numel() == W.numel(), "zW shape");
+  }
+  if (opt_mode == 2) {
+    CHK(zV.has_value(), "FTRL on V needs zV");
+    check_cuda_f32(*zV, "zV");
+    CHK(zV->numel() == V.numel(), "zV shape");
+  }
+  const int* perm_ptr = nullptr;
+  at::Tensor perm_i;
+  if (perm.has_value()) {
+    perm_i = perm32(*perm).contiguous();
+    CHK(perm_i.is_cuda() && perm_i.numel() == nnz, "perm shape");
+    perm_ptr = perm_i.data_ptr<int>();
+  }
+  const int num_cus =
+      at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  lightctr::fm_segment_apply_launch(
+      sorted_fids.data_ptr<int>(), perm_ptr, piece_start.data_ptr<int>(),
+      n_pieces.data_ptr<int>(), gw.data_ptr<float>(), gv.data_ptr<float>(),
+      gradW.data_ptr<float>(), gradV.data_ptr<float>(),
+      spill.data_ptr<int>(), spill_count.data_ptr<int>(), (int)spill.numel(),
+      (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), W.data_ptr<float>(),
+      nW.data_ptr<float>(),
+      zW.has_value() ? zW->data_ptr<float>() : nullptr, nV.data_ptr<float>(),
+      zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
+      (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
+      num_cus, cur_stream());
+}
+
 // ---- FFM ----
 
 at::Tensor ffm_forward(at::Tensor row_ptr, at::Tensor fields, at::Tensor fids,
@@ -1056,6 +1157,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("p0"), py::arg("p1"), py::arg("p2"), py::arg("p3"),
         py::arg("v_lr") = 0.05, py::arg("v_eps") = 1e-8,
         py::arg("v_l2") = 1e-5);
+  m.def("segment_worklist", &segment_worklist,
+        "piece starts of a sorted id stream -> (piece_start, n_pieces)",
+        py::arg("sorted_fids"), py::arg("cap"),
+        py::arg("reset") = py::none());
+  m.def("fm_segment_apply", &fm_segment_apply,
+        "per-piece segment reduce + fused optimizer; partial pieces spill",
+        py::arg("sorted_fids"), py::arg("perm"), py::arg("piece_start"),
+        py::arg("n_pieces"), py::arg("gw"), py::arg("gv"), py::arg("gradW"),
+        py::arg("gradV"), py::arg("spill"), py::arg("spill_count"),
+        py::arg("W"), py::arg("V"), py::arg("nW"), py::arg("nV"),
+        py::arg("zW"), py::arg("zV"), py::arg("opt_mode"), py::arg("p0"),
+        py::arg("p1"), py::arg("p2"), py::arg("p3"), py::arg("v_lr") = 0.05,
+        py::arg("v_eps") = 1e-8, py::arg("v_l2") = 1e-5);
   m.def("ffm_forward", &ffm_forward, "FFM pairwise forward (LDS-staged)");
   m.def("ffm_forward_pp", &ffm_forward_pp, "lane-per-pair FFM forward");
   m.def("ffm_row_emit", &ffm_row_emit,

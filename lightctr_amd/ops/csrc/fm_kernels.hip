@@ -14,32 +14,102 @@
 //
 // All buffers live in HBM3E; the whole step is 5 kernel launches and is
 // hipGraph-capturable (no device->host syncs).
+#include <algorithm>
 #include <cstdio>
 #include "common.h"
 
 namespace lightctr {
 
+// Optimizer update bodies, on register values: every FM kernel that applies
+// an update (sparse apply over a fid list, the walk's fused flush, the
+// segment reduce) loads the state, calls one of these and stores it back,
+// so the arithmetic exists once.
+//
 // FTRL-proximal (per-coordinate), semantics of the reference FTRL updater
 // (gradientUpdater.h:235-278): z,n state per parameter.
+__device__ __forceinline__ void ftrl_step(float& w, float& z, float& n,
+                                          float g, float alpha, float beta,
+                                          float l1, float l2) {
+  const float g2 = g * g;
+  const float nold = n;
+  const float sigma = (sqrtf(nold + g2) - sqrtf(nold)) / alpha;
+  const float znew = z + g - sigma * w;
+  const float nnew = nold + g2;
+  z = znew;
+  n = nnew;
+  if (fabsf(znew) <= l1) {
+    w = 0.f;
+  } else {
+    w = -(znew - copysignf(l1, znew)) / ((beta + sqrtf(nnew)) / alpha + l2);
+  }
+}
+
+// Adagrad with L2 folded into the gradient.
+__device__ __forceinline__ void adagrad_step(float& w, float& n, float g_in,
+                                             float lr, float eps, float l2) {
+  const float g = g_in + l2 * w;
+  const float a = n + g * g;
+  n = a;
+  w -= lr * g * __frsqrt_rn(a + eps);
+}
+
 __device__ __forceinline__ void ftrl_update(float* __restrict__ w,
                                             float* __restrict__ z,
                                             float* __restrict__ n, float g,
                                             float alpha, float beta, float l1,
                                             float l2) {
-  const float g2 = g * g;
-  const float nold = *n;
-  const float sigma = (sqrtf(nold + g2) - sqrtf(nold)) / alpha;
-  const float znew = *z + g - sigma * (*w);
-  const float nnew = nold + g2;
-  *z = znew;
-  *n = nnew;
-  if (fabsf(znew) <= l1) {
-    *w = 0.f;
+  float wv = *w, zv = *z, nv = *n;
+  ftrl_step(wv, zv, nv, g, alpha, beta, l1, l2);
+  *z = zv;
+  *n = nv;
+  *w = wv;
+}
+
+__device__ __forceinline__ void adagrad_update(float* __restrict__ w,
+                                               float* __restrict__ n, float g,
+                                               float lr, float eps,
+                                               float l2) {
+  float wv = *w, nv = *n;
+  adagrad_step(wv, nv, g, lr, eps, l2);
+  *n = nv;
+  *w = wv;
+}
+
+// Optimizer state + knobs for the kernels that fuse the update into the
+// gradient reduction. opt_mode: 1 = Adagrad, 2 = FTRL, 3 = FTRL on W +
+// Adagrad on V (the default FM pairing, models/fm.py ftrl_v="adagrad").
+struct FmOptArgs {
+  float* W;
+  float* nW;
+  float* zW;
+  float* nV;
+  float* zV;
+  float p0, p1, p2, p3;  // adagrad: lr, eps, l2 | ftrl: alpha, beta, l1, l2
+  float q0, q1, q2;      // opt_mode 3, V side: v_lr, v_eps, v_l2
+};
+
+// one latent factor / one linear weight under opt_mode (z unused by Adagrad)
+__device__ __forceinline__ void fm_opt_step_v(int opt_mode, float& v,
+                                              float& n, float& z, float g,
+                                              const FmOptArgs& oa) {
+  if (opt_mode == 1) {
+    adagrad_step(v, n, g, oa.p0, oa.p1, oa.p2);
+  } else if (opt_mode == 3) {
+    adagrad_step(v, n, g, oa.q0, oa.q1, oa.q2);
   } else {
-    *w = -(znew - copysignf(l1, znew)) / ((beta + sqrtf(nnew)) / alpha + l2);
+    ftrl_step(v, z, n, g, oa.p0, oa.p1, oa.p2, oa.p3);
   }
 }
 
+__device__ __forceinline__ void fm_opt_step_w(int opt_mode, float& w,
+                                              float& n, float& z, float g,
+                                              const FmOptArgs& oa) {
+  if (opt_mode == 1) {
+    adagrad_step(w, n, g, oa.p0, oa.p1, oa.p2);
+  } else {
+    ftrl_step(w, z, n, g, oa.p0, oa.p1, oa.p2, oa.p3);
+  }
+}
 
 // ---------------------------------------------------------------------------
 // Forward: pred[row] = sum_j w[fid]*x + 0.5*(||sumVX||^2 - sum_j ||v*x||^2)
@@ -247,18 +317,6 @@ __global__ void inv_perm_kernel(const int* __restrict__ perm,
 //           time, so the optimizer update is applied in place with no
 //           atomics and the slab/bitmap/compaction/apply pass only handles
 //           the ~2 boundary-spanning features per subgroup.
-struct FmOptArgs {
-  float* W;
-  float* nW;
-  float* zW;
-  float* nV;
-  float* zV;
-  float p0, p1, p2, p3;  // adagrad: lr, eps, l2 | ftrl: alpha, beta, l1, l2
-  // opt_mode 3 (FTRL on W + Adagrad on V — the default FM optimizer
-  // pairing, models/fm.py ftrl_v="adagrad"): q* are the V-side knobs
-  float q0, q1, q2;  // v_lr, v_eps, v_l2
-};
-
 // WPE: min waves/SIMD handed to the allocator (HIP __launch_bounds__
 // 2nd arg). The K=16 walk allocates 86 VGPR — one register over the
 // 6-wave boundary (512/6 = 85.3); WPE=6 caps it at 85 for +20%
@@ -298,33 +356,19 @@ __global__ __launch_bounds__(256, WPE) void fm_sorted_apply_kernel(
     if (opt_mode != 0 && head_ok && tail_ok) {
       // exclusive owner of this feature's total gradient: fused update
       const size_t off = (size_t)cur_fid * K + k;
-      if (opt_mode == 1) {  // adagrad
-        const float gg = acc + oa.p2 * V[off];
-        const float a = oa.nV[off] + gg * gg;
-        oa.nV[off] = a;
-        V[off] -= oa.p0 * gg * __frsqrt_rn(a + oa.p1);
-        if (k == 0) {
-          const float gwv = accw + oa.p2 * oa.W[cur_fid];
-          const float aw = oa.nW[cur_fid] + gwv * gwv;
-          oa.nW[cur_fid] = aw;
-          oa.W[cur_fid] -= oa.p0 * gwv * __frsqrt_rn(aw + oa.p1);
-        }
-      } else if (opt_mode == 3) {  // FTRL on W, Adagrad on V
-        const float gg = acc + oa.q2 * V[off];
-        const float a = oa.nV[off] + gg * gg;
-        oa.nV[off] = a;
-        V[off] -= oa.q0 * gg * __frsqrt_rn(a + oa.q1);
-        if (k == 0) {
-          ftrl_update(&oa.W[cur_fid], &oa.zW[cur_fid], &oa.nW[cur_fid],
-                      accw, oa.p0, oa.p1, oa.p2, oa.p3);
-        }
-      } else {  // ftrl
-        ftrl_update(&V[off], &oa.zV[off], &oa.nV[off], acc, oa.p0, oa.p1,
-                    oa.p2, oa.p3);
-        if (k == 0) {
-          ftrl_update(&oa.W[cur_fid], &oa.zW[cur_fid], &oa.nW[cur_fid],
-                      accw, oa.p0, oa.p1, oa.p2, oa.p3);
-        }
+      float v = V[off], n = oa.nV[off];
+      float z = opt_mode == 2 ? oa.zV[off] : 0.f;
+      fm_opt_step_v(opt_mode, v, n, z, acc, oa);
+      if (opt_mode == 2) oa.zV[off] = z;
+      oa.nV[off] = n;
+      V[off] = v;
+      if (k == 0) {
+        float w = oa.W[cur_fid], nw = oa.nW[cur_fid];
+        float zw = opt_mode != 1 ? oa.zW[cur_fid] : 0.f;
+        fm_opt_step_w(opt_mode, w, nw, zw, accw, oa);
+        if (opt_mode != 1) oa.zW[cur_fid] = zw;
+        oa.nW[cur_fid] = nw;
+        oa.W[cur_fid] = w;
       }
     } else if (head_ok && tail_ok) {
       // exclusive owner of the whole segment: the slabs are zero for every
@@ -599,6 +643,161 @@ __global__ void fm_segscan4_apply_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Segment backward (backward_mode="segment"): per-piece reduce with the
+// optimizer fused in. The sorted stream is cut beforehand (sort_kernels.hip,
+// segment_worklist_launch) into pieces: a piece starts at every run head and
+// at every multiple of CAP, so it lies inside one run and is at most CAP
+// long. One K-lane subgroup sums one piece; the loop has no neighbour
+// comparison, and the loads of a batch are independent.
+//   * WHOLE piece (starts at its run's head, ends at its tail): the subgroup
+//     holds the feature's total batch gradient and applies the optimizer in
+//     place — no slab, no bitmap, no atomics.
+//   * PARTIAL piece (its run crosses a CAP boundary): atomicAdd into the
+//     gradW/gradV slabs; the piece holding the run's head appends the fid to
+//     the spill list (one counter atomic per wave), which the sparse apply
+//     kernels below consume, re-zeroing the slab entries they read.
+// At most ceil(nnz/CAP)-1 runs cross a boundary, which bounds the list.
+// The grid is fixed; waves stride over the device-side piece count. Per
+// piece the dependent loads are piece_start -> (fid, perm) -> (gv, V, nV,
+// neighbours): the first two levels are fetched one and two iterations
+// ahead, so an iteration waits for one round trip, not three.
+// ---------------------------------------------------------------------------
+template <int K>
+__global__ __launch_bounds__(256) void fm_segment_apply_kernel(
+    const int* __restrict__ sorted_fids, const int* __restrict__ perm,
+    const int* __restrict__ piece_start, const int* __restrict__ n_pieces,
+    const float* __restrict__ gw, const float* __restrict__ gv,
+    float* __restrict__ gradW, float* __restrict__ gradV,
+    int* __restrict__ spill, int* __restrict__ spill_count, int spill_cap,
+    int nnz, int opt_mode, float* __restrict__ V, FmOptArgs oa) {
+  constexpr int G = LCTR_WAVE / K;
+  const int lane = threadIdx.x & (LCTR_WAVE - 1);
+  const int g = lane / K;
+  const int k = lane % K;
+  const long P = min(*n_pieces, nnz);
+  const long stride = (long)gridDim.x * (blockDim.x / LCTR_WAVE) * G;
+  long base =
+      ((long)blockIdx.x * (blockDim.x / LCTR_WAVE) + (threadIdx.x >> 6)) * G;
+
+  // [s, e) of this subgroup's piece in the wave's group at `b`; a subgroup
+  // past the last piece gets the empty piece s = e = nnz
+  auto load_piece = [&](long b, int& s, int& e) {
+    const long p = b + g;
+    s = nnz;
+    e = nnz;
+    if (p < P) {
+      s = min(max(piece_start[p], 0), nnz);
+      if (p + 1 < P) e = min(max(piece_start[p + 1], s), nnz);
+    }
+  };
+  auto load_head = [&](int s, int& fid, long& src) {
+    fid = -1;
+    src = 0;
+    if (s < nnz) {
+      fid = sorted_fids[s];
+      src = perm ? (long)perm[s] : (long)s;
+    }
+  };
+
+  int s0, e0, s1, e1, fid0;
+  long src0;
+  load_piece(base, s0, e0);
+  load_piece(base + stride, s1, e1);
+  load_head(s0, fid0, src0);
+
+  // wave-uniform loop: every lane stays in it until the wave's last group,
+  // so the ballot below sees the whole wave
+  for (; base < P; base += stride) {
+    int s2, e2, fid1;
+    long src1;
+    load_piece(base + 2 * stride, s2, e2);
+    load_head(s1, fid1, src1);
+
+    bool spill_me = false;
+    if (s0 < nnz) {
+      const int fid = fid0;
+      const size_t off = (size_t)fid * K + k;
+      // everything the piece needs besides its own entries depends on fid
+      // alone: issue it with the first gradient row
+      float acc = gv[(size_t)src0 * K + k];
+      float accw = (k == 0) ? gw[src0] : 0.f;
+      const bool head = (s0 == 0) || (sorted_fids[s0 - 1] != fid);
+      const bool tail = (e0 >= nnz) || (sorted_fids[e0] != fid);
+      float v = V[off], n = oa.nV[off];
+      float z = (opt_mode == 2) ? oa.zV[off] : 0.f;
+      float w = 0.f, nw = 0.f, zw = 0.f;
+      if (k == 0) {
+        w = oa.W[fid];
+        nw = oa.nW[fid];
+        if (opt_mode != 1) zw = oa.zW[fid];
+      }
+      // rest of the piece, 8 independent row loads per batch; the batch's
+      // source slots (perm) are fetched one batch ahead, so a batch costs
+      // one round trip, not perm -> gv
+      int src[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int ee = s0 + 1 + u;
+        src[u] = (perm && ee < e0) ? perm[ee] : ee;
+      }
+      for (int e = s0 + 1; e < e0; e += 8) {
+        float tv[8], tw[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          tv[u] = 0.f;
+          tw[u] = 0.f;
+          if (e + u < e0) {
+            tv[u] = gv[(size_t)src[u] * K + k];
+            if (k == 0) tw[u] = gw[src[u]];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int ee = e + 8 + u;
+          src[u] = (perm && ee < e0) ? perm[ee] : ee;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          acc += tv[u];
+          accw += tw[u];
+        }
+      }
+      if (head && tail) {
+        fm_opt_step_v(opt_mode, v, n, z, acc, oa);
+        if (opt_mode == 2) oa.zV[off] = z;
+        oa.nV[off] = n;
+        V[off] = v;
+        if (k == 0) {
+          fm_opt_step_w(opt_mode, w, nw, zw, accw, oa);
+          if (opt_mode != 1) oa.zW[fid] = zw;
+          oa.nW[fid] = nw;
+          oa.W[fid] = w;
+        }
+      } else {
+        atomicAdd(&gradV[off], acc);
+        if (k == 0) atomicAdd(&gradW[fid], accw);
+        spill_me = head && (k == 0);
+      }
+    }
+    // wave-aggregated append of the runs that spilled to the slabs
+    const unsigned long long m = __ballot(spill_me);
+    if (m) {
+      int slot = 0;
+      if (lane == 0) slot = atomicAdd(spill_count, __popcll(m));
+      slot = __shfl(slot, 0) + __popcll(m & ((1ull << lane) - 1ull));
+      if (spill_me && slot < spill_cap) spill[slot] = fid0;  // clamp
+    }
+
+    s0 = s1;
+    e0 = e1;
+    fid0 = fid1;
+    src0 = src1;
+    s1 = s2;
+    e1 = e2;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Bitmap -> unique-fid list compaction. One thread per 64-feature word;
 // clears the word as it goes so the bitmap is reusable next step.
 // ---------------------------------------------------------------------------
@@ -665,16 +864,10 @@ __global__ void fm_adagrad_apply_kernel(
   if (i >= capacity || i >= *count) return;
   const int fid = uniq[i];
   const size_t off = (size_t)fid * K + k;
-  const float g = gradV[off] + l2 * V[off];
-  const float acc = nV[off] + g * g;
-  nV[off] = acc;
-  V[off] -= lr * g * __frsqrt_rn(acc + eps);
+  adagrad_update(&V[off], &nV[off], gradV[off], lr, eps, l2);
   gradV[off] = 0.f;
   if (k == 0) {
-    const float gw = gradW[fid] + l2 * W[fid];
-    const float a = nW[fid] + gw * gw;
-    nW[fid] = a;
-    W[fid] -= lr * gw * __frsqrt_rn(a + eps);
+    adagrad_update(&W[fid], &nW[fid], gradW[fid], lr, eps, l2);
     gradW[fid] = 0.f;
   }
 }
@@ -698,10 +891,7 @@ __global__ void fm_ftrl_apply_kernel(
   const int fid = uniq[i];
   const size_t off = (size_t)fid * K + k;
   if (v_adagrad) {
-    const float g = gradV[off] + v_l2 * V[off];
-    const float acc = nV[off] + g * g;
-    nV[off] = acc;
-    V[off] -= v_lr * g * __frsqrt_rn(acc + v_eps);
+    adagrad_update(&V[off], &nV[off], gradV[off], v_lr, v_eps, v_l2);
   } else {
     ftrl_update(&V[off], &zV[off], &nV[off], gradV[off], alpha, beta, l1,
                 l2);
@@ -857,6 +1047,47 @@ void fm_sorted_apply_launch(const int* sorted_fids, const int* perm,
                                      perm, gw, gv, gradW, gradV, touched,
                                      nnz, chunk, opt_mode, V, oa));
   }
+}
+
+// resident 256-thread blocks of the segment kernel per CU (register bound)
+template <int K>
+static int fm_segment_blocks_per_cu() {
+  static const int nb = [] {
+    int n = 0;
+    LCTR_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &n, fm_segment_apply_kernel<K>, waves_per_block() * LCTR_WAVE, 0));
+    return std::max(n, 1);
+  }();
+  return nb;
+}
+
+void fm_segment_apply_launch(const int* sorted_fids, const int* perm,
+                             const int* piece_start, const int* n_pieces,
+                             const float* gw, const float* gv, float* gradW,
+                             float* gradV, int* spill, int* spill_count,
+                             int spill_cap, int nnz, int K, int opt_mode,
+                             float* V, float* W, float* nW, float* zW,
+                             float* nV, float* zV, float p0, float p1,
+                             float p2, float p3, float q0, float q1, float q2,
+                             int num_cus, hipStream_t stream) {
+  if (nnz <= 0) return;
+  // fixed grid: exactly the blocks the device holds at once (a block more
+  // per CU would run as a second round), never more than one subgroup per
+  // possible piece
+  const int wpb = waves_per_block();
+  const int G = LCTR_WAVE / K;
+  int per_cu = 1;
+  DISPATCH_K(K, per_cu = fm_segment_blocks_per_cu<KC>());
+  const long need = ((long)nnz + (long)wpb * G - 1) / ((long)wpb * G);
+  const int blocks =
+      (int)std::max(1L, std::min(need, (long)per_cu * std::max(num_cus, 1)));
+  FmOptArgs oa{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1, q2};
+  DISPATCH_K(K, hipLaunchKernelGGL((fm_segment_apply_kernel<KC>),
+                                   dim3(blocks), dim3(wpb * LCTR_WAVE), 0,
+                                   stream, sorted_fids, perm, piece_start,
+                                   n_pieces, gw, gv, gradW, gradV, spill,
+                                   spill_count, spill_cap, nnz, opt_mode, V,
+                                   oa));
 }
 
 void bitmap_compact_launch(unsigned long long* bitmap, int nwords,

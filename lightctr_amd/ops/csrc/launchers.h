@@ -32,6 +32,15 @@ void fm_sorted_apply_launch(const int* sorted_fids, const int* perm,
                             float p0, float p1, float p2, float p3,
                             float q0, float q1, float q2,
                             int chunk, ihipStream_t* stream);
+void fm_segment_apply_launch(const int* sorted_fids, const int* perm,
+                             const int* piece_start, const int* n_pieces,
+                             const float* gw, const float* gv, float* gradW,
+                             float* gradV, int* spill, int* spill_count,
+                             int spill_cap, int nnz, int K, int opt_mode,
+                             float* V, float* W, float* nW, float* zW,
+                             float* nV, float* zV, float p0, float p1,
+                             float p2, float p3, float q0, float q1, float q2,
+                             int num_cus, ihipStream_t* stream);
 void bitmap_compact_launch(unsigned long long* bitmap, int nwords,
                            int* out_fids, int* out_count, int cap,
                            ihipStream_t* stream);
@@ -239,6 +248,13 @@ void radix_sort_pairs_i32_launch(void* temp, unsigned long temp_bytes,
                                  const int* keys_in, int* keys_out,
                                  const int* vals_in, int* vals_out, int n,
                                  int end_bit, ihipStream_t* stream);
+// work list of the segment backward: compacted piece starts of a sorted
+// stream + their count (device side); zero_me (optional) is reset to 0
+unsigned long segment_worklist_temp_bytes(int n);
+void segment_worklist_launch(void* temp, unsigned long temp_bytes,
+                             const int* sorted, int n, int cap,
+                             int* piece_start, int* n_pieces, int* zero_me,
+                             ihipStream_t* stream);
 
 // --- gbm_kernels.hip ---
 void gbm_hist_launch(const unsigned char* bins, const float* grad,

@@ -65,6 +65,36 @@ def main():
                -4: "walk-pp2"}.get(chunk, f"walk{chunk}")
         print(f"apply {tag:8s}  gather {a:8.1f} us   seq {b:8.1f} us")
 
+    # segment mode: work list + per-piece reduce with the optimizer fused
+    # in + spill apply. This row replaces walk + bitmap_compact + sparse
+    # apply, so the two-phase total is printed next to it.
+    def two_phase():
+        ops.fm_sorted_apply(sorted_fids, perm, gw_s, gv_s, m.gradW, m.gradV,
+                            m.touched, 0)
+        m.count.zero_()
+        ops.bitmap_compact(m.touched, m.uniq, m.count)
+        m._sparse_apply(ops, m.uniq[: min(m.uniq.numel(), nnz)])
+
+    print(f"apply walk384 + compact + sparse apply  {t(two_phase):8.1f} us")
+    for cap in (32, 64, 128, 256, 512):
+        def segment():
+            ps, npc = ops.segment_worklist(sorted_fids, cap, m.count)
+            spill = m.uniq[: min(m.uniq.numel(), nnz // cap + 1)]
+            ops.fm_segment_apply(
+                sorted_fids, perm, ps, npc, gw_s, gv_s, m.gradW, m.gradV,
+                spill, m.count, m.W, m.V, m.nW, m.nV, m.zW, None, 3,
+                h.ftrl_alpha, h.ftrl_beta, h.ftrl_l1, h.ftrl_l2,
+                v_lr=h.lr, v_eps=h.eps, v_l2=h.l2)
+            m._sparse_apply(ops, spill)
+            return ps, npc
+
+        wl = t(lambda: ops.segment_worklist(sorted_fids, cap, m.count))
+        tot = t(segment)
+        ps, npc = segment()
+        print(f"apply segment cap={cap:4d}  worklist {wl:6.1f} us   "
+              f"worklist+reduce+spill apply {tot:8.1f} us   "
+              f"pieces {int(npc)} spilled {int(m.count)}")
+
     # correctness cross-check: gather vs scatter paths agree
     m.gradW.zero_(); m.gradV.zero_(); m.touched.zero_()
     ops.fm_sorted_apply(sorted_fids, perm, gw_s, gv_s, m.gradW, m.gradV,
@@ -94,10 +124,21 @@ def main():
     # full-step A/B: fused mode-3 apply vs two-phase (default ftrl pairing)
     for fused in (False, True):
         mm = FMModel(h, device="cuda")
+        mm.backward_mode = "sorted"
         mm.fused_apply = fused
         tt = t(lambda: mm.train_step(row_ptr, fids, vals, labels))
-        print(f"step fused={int(fused)}  {tt:8.1f} us  "
+        print(f"step sorted fused={int(fused)}  {tt:8.1f} us  "
               f"({65536 / tt:.1f}M ex/s)")
+        del mm
+    # ... vs the segment mode at each CAP (eager launches, no hipGraph)
+    for cap in (32, 64, 128, 256, 512):
+        mm = FMModel(h, device="cuda")
+        mm.backward_mode = "segment"
+        mm.segment_cap = cap
+        tt = t(lambda: mm.train_step(row_ptr, fids, vals, labels))
+        print(f"step segment cap={cap:4d}  {tt:8.1f} us  "
+              f"({65536 / tt:.1f}M ex/s)")
+        del mm
 
 
 if __name__ == "__main__":
