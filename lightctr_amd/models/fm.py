@@ -7,10 +7,13 @@ Adagrad apply) — rebuilt GPU-first:
 
   * parameters W [F] and V [F,K] are flat fp32 slabs resident in HBM3E
   * the train step is a handful of HIP kernel launches with no device->host
-    syncs: forward, loss, per-entry gradient emit, radix sort, then (default
-    backward_mode="segment") a work-list pass and a per-piece segment reduce
-    with the optimizer fused in; "sorted" (walk into slabs + bitmap compact
-    + sparse optimizer) and "atomic" (scatter backward) stay selectable
+    syncs. Default backward_mode="segment": training forward (loss and
+    per-entry (row, x) records fused in), radix sort with the records as
+    payload, a work-list pass and a per-piece segment reduce that recomputes
+    the gradients and applies the optimizer in place. "segment_emit" (the
+    same reduce fed by a per-entry gradient emit), "sorted" (walk into slabs
+    + bitmap compact + sparse optimizer) and "atomic" (scatter backward)
+    stay selectable
   * CPU path uses the fp32 torch reference ops (same math; the test oracle)
   * optimizers: adagrad (reference default) and FTRL-proximal (BASELINE
     config #2: "FM k=16 ... FTRL fused update"); both are applied only to
@@ -25,7 +28,7 @@ from dataclasses import dataclass
 import torch
 
 from ..ops import fm_ref
-from ..ops._extension import require_hip_ops, sort_ids
+from ..ops._extension import require_hip_ops, sort_ids, sort_ids_rec
 from ..utils.checks import validate_csr_batch
 from ..utils.metrics import auc_score
 
@@ -78,12 +81,18 @@ class FMModel:
         self.uniq = torch.zeros(cap, dtype=torch.int32, device=self.device)
         self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._use_hip = self.device.type == "cuda"
-        # "segment" (default) | "sorted" | "atomic"
+        # "segment" (default) | "segment_emit" | "sorted" | "atomic"
         # segment: sort, then one K-lane subgroup per piece (a run of equal
         # fids cut at multiples of segment_cap) sums its gradients and, for
         # a run that fits one piece, applies the optimizer in place; only
         # runs crossing a cut go through the slabs + the sparse apply, with
         # uniq/count as their spill list. No bitmap pass in this mode.
+        # The training forward writes one (row, x) record per entry, the
+        # sort carries it as payload and the reduce recomputes each entry's
+        # gradient from it: no per-entry gradient buffer, no loss kernel.
+        # segment_emit: the same reduce fed by fm_backward_emit's per-entry
+        # gradients through the sort permutation (the earlier pipeline,
+        # kept for A/B).
         self.backward_mode = "segment"
         self.segment_cap = 256  # power of two; sweep in docs/KERNELS.md
         # fused-apply: interior feature segments get their optimizer update
@@ -121,15 +130,21 @@ class FMModel:
         validate_csr_batch(row_ptr, fids, vals, self.h.num_features)
         if self._use_hip:
             ops = require_hip_ops()
-            pred, sumVX = ops.fm_forward(row_ptr, fids, vals, self.W, self.V)
-            loss, dpred = ops.logloss_grad(pred, labels, scale)
             # fused_apply is a variant of the walk: asking for it selects
             # the sorted path
             if self.backward_mode == "segment" and not self.fused_apply:
-                self._segment_backward(ops, row_ptr, fids, vals, sumVX,
-                                       dpred)
+                loss, dpred, sumVX, rec = ops.fm_forward_train(
+                    row_ptr, fids, vals, self.W, self.V, labels, scale)
+                self._segment_backward(ops, fids, sumVX, dpred, rec)
                 return loss
-            if self.backward_mode in ("sorted", "segment"):
+            pred, sumVX = ops.fm_forward(row_ptr, fids, vals, self.W, self.V)
+            loss, dpred = ops.logloss_grad(pred, labels, scale)
+            if (self.backward_mode == "segment_emit"
+                    and not self.fused_apply):
+                self._segment_emit_backward(ops, row_ptr, fids, vals, sumVX,
+                                            dpred)
+                return loss
+            if self.backward_mode in ("sorted", "segment", "segment_emit"):
                 # contention-free backward: emit per-entry grads
                 # (coalesced), bit-range radix-sort the fids, then
                 # segment-reduce into the slabs with interior-store
@@ -223,14 +238,11 @@ class FMModel:
                                  self.nW, self.nV, self.gradW, self.gradV,
                                  self.h.lr, self.h.eps, self.h.l2)
 
-    def _segment_backward(self, ops, row_ptr, fids, vals, sumVX, dpred):
-        nnz = fids.numel()
-        if nnz == 0:
-            return
+    def _segment_pieces(self, ops, sorted_fids):
+        """Work list + spill list + optimizer arguments shared by the two
+        segment modes."""
+        nnz = sorted_fids.numel()
         cap = int(self.segment_cap)
-        sorted_fids, perm = sort_ids(fids, self.h.num_features)
-        gw, gv = ops.fm_backward_emit(row_ptr, fids, vals, self.V, sumVX,
-                                      dpred)
         # the work-list pass also resets the spill counter
         piece_start, n_pieces = ops.segment_worklist(sorted_fids, cap,
                                                      self.count)
@@ -242,11 +254,37 @@ class FMModel:
         else:
             knobs = (self.h.ftrl_alpha, self.h.ftrl_beta, self.h.ftrl_l1,
                      self.h.ftrl_l2)
-        ops.fm_segment_apply(
-            sorted_fids, perm, piece_start, n_pieces, gw, gv, self.gradW,
-            self.gradV, spill, self.count, self.W, self.V, self.nW, self.nV,
-            self.zW if mode != 1 else None, self.zV if mode == 2 else None,
-            mode, *knobs, v_lr=self.h.lr, v_eps=self.h.eps, v_l2=self.h.l2)
+        tail = (piece_start, n_pieces, self.gradW, self.gradV, spill,
+                self.count, self.W, self.V, self.nW, self.nV,
+                self.zW if mode != 1 else None,
+                self.zV if mode == 2 else None, mode, *knobs)
+        kw = dict(v_lr=self.h.lr, v_eps=self.h.eps, v_l2=self.h.l2)
+        return spill, tail, kw
+
+    def _segment_backward(self, ops, fids, sumVX, dpred, rec):
+        """Recompute reduce: the sort carries the forward's (row, x) records
+        and the reduce forms every entry's gradient itself."""
+        if fids.numel() == 0:
+            return
+        sorted_fids, sorted_rec = sort_ids_rec(fids, rec,
+                                               self.h.num_features)
+        spill, tail, kw = self._segment_pieces(ops, sorted_fids)
+        ops.fm_segment_apply_rec(sorted_fids, sorted_rec, sumVX, dpred,
+                                 *tail, **kw)
+        self._sparse_apply(ops, spill)
+
+    def _segment_emit_backward(self, ops, row_ptr, fids, vals, sumVX, dpred):
+        """Emit-fed reduce (backward_mode="segment_emit"): per-entry
+        gradients written in CSR order and gathered through the sort
+        permutation."""
+        if fids.numel() == 0:
+            return
+        sorted_fids, perm = sort_ids(fids, self.h.num_features)
+        gw, gv = ops.fm_backward_emit(row_ptr, fids, vals, self.V, sumVX,
+                                      dpred)
+        spill, tail, kw = self._segment_pieces(ops, sorted_fids)
+        ops.fm_segment_apply(sorted_fids, perm, tail[0], tail[1], gw, gv,
+                             *tail[2:], **kw)
         self._sparse_apply(ops, spill)
 
     # -- checkpoint (reference saveModel/loadModel, fm_algo_abst.h:109-135) --

@@ -52,3 +52,10 @@ def sort_ids(fids, upper: int):
     the live bit range (2-3 passes instead of 4; see sort_kernels.hip)."""
     end_bit = max(1, int(upper - 1).bit_length())
     return require_hip_ops().radix_sort_index(fids, end_bit)
+
+
+def sort_ids_rec(fids, rec, upper: int):
+    """(sorted, sorted_rec): the same bit-range sort carrying one 8-byte
+    record per id (rec int32 [n, 2]) as its payload instead of an index."""
+    end_bit = max(1, int(upper - 1).bit_length())
+    return require_hip_ops().radix_sort_rec(fids, rec, end_bit)

@@ -61,6 +61,45 @@ std::vector<at::Tensor> fm_forward(at::Tensor row_ptr, at::Tensor fids,
   return {pred, sumVX};
 }
 
+// [n, 2] int32 records {row, bits of x}; read and written as 8-byte words
+void check_cuda_rec(const at::Tensor& t, long n, const char* name) {
+  check_cuda_i32(t, name);
+  CHK(t.dim() == 2 && t.size(0) == n && t.size(1) == 2, name,
+      " must be [n, 2]");
+  CHK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 8 == 0, name,
+      " must be 8-byte aligned");
+}
+
+// Training forward: fm_forward + logloss_grad in one launch, plus the
+// per-entry records rec[j] = {row of j, bits of vals[j]} that the segment
+// backward sorts by fid. Returns (loss, dpred, sumVX, rec).
+std::vector<at::Tensor> fm_forward_train(at::Tensor row_ptr, at::Tensor fids,
+                                         at::Tensor vals, at::Tensor W,
+                                         at::Tensor V, at::Tensor label,
+                                         double scale) {
+  check_cuda_i32(row_ptr, "row_ptr");
+  check_cuda_i32(fids, "fids");
+  check_cuda_f32(vals, "vals");
+  check_cuda_f32(W, "W");
+  check_cuda_f32(V, "V");
+  check_cuda_f32(label, "label");
+  const int B = (int)row_ptr.numel() - 1;
+  const int K = (int)V.size(1);
+  const long nnz = fids.numel();
+  CHK(vals.numel() == nnz, "vals must have one value per entry");
+  CHK(label.numel() == B, "label must have one value per row");
+  auto loss = at::empty({B}, W.options());
+  auto dpred = at::empty({B}, W.options());
+  auto sumVX = at::empty({B, K}, W.options());
+  auto rec = at::empty({nnz, 2}, fids.options());
+  lightctr::fm_forward_train_launch(
+      row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
+      W.data_ptr<float>(), V.data_ptr<float>(), label.data_ptr<float>(),
+      (float)scale, loss.data_ptr<float>(), dpred.data_ptr<float>(),
+      sumVX.data_ptr<float>(), rec.data_ptr<int>(), B, K, cur_stream());
+  return {loss, dpred, sumVX, rec};
+}
+
 std::vector<at::Tensor> logloss_grad(at::Tensor pred, at::Tensor label,
                                      double scale) {
   check_cuda_f32(pred, "pred");
@@ -220,27 +259,22 @@ std::vector<at::Tensor> segment_worklist(at::Tensor sorted_fids, int64_t cap,
   return {piece_start, n_pieces};
 }
 
-// Segment backward: one K-lane subgroup per piece of the work list sums the
-// piece's gradients; whole pieces get the optimizer update in place,
-// partial ones go to the slabs and `spill` (fid list + counter, consumed by
-// fm_adagrad_apply / fm_ftrl_apply). opt_mode as in fm_sorted_apply_fused.
-void fm_segment_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
-                      at::Tensor piece_start, at::Tensor n_pieces,
-                      at::Tensor gw, at::Tensor gv, at::Tensor gradW,
-                      at::Tensor gradV, at::Tensor spill,
-                      at::Tensor spill_count, at::Tensor W, at::Tensor V,
-                      at::Tensor nW, at::Tensor nV,
-                      c10::optional<at::Tensor> zW,
-                      c10::optional<at::Tensor> zV, int64_t opt_mode,
-                      double p0, double p1, double p2, double p3, double v_lr,
-                      double v_eps, double v_l2) {
+// Argument checks shared by the two entry sources of the segment backward
+void check_segment_common(const at::Tensor& sorted_fids,
+                          const at::Tensor& piece_start,
+                          const at::Tensor& n_pieces, const at::Tensor& gradW,
+                          const at::Tensor& gradV, const at::Tensor& spill,
+                          const at::Tensor& spill_count, const at::Tensor& W,
+                          const at::Tensor& V, const at::Tensor& nW,
+                          const at::Tensor& nV,
+                          const c10::optional<at::Tensor>& zW,
+                          const c10::optional<at::Tensor>& zV,
+                          int64_t opt_mode) {
   check_cuda_i32(sorted_fids, "sorted_fids");
   check_cuda_i32(piece_start, "piece_start");
   check_cuda_i32(n_pieces, "n_pieces");
   check_cuda_i32(spill, "spill");
   check_cuda_i32(spill_count, "spill_count");
-  check_cuda_f32(gw, "gw");
-  check_cuda_f32(gv, "gv");
   check_cuda_f32(gradW, "gradW");
   check_cuda_f32(gradV, "gradV");
   check_cuda_f32(W, "W");
@@ -251,7 +285,6 @@ void fm_segment_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
   const int K = (int)V.size(1);
   CHK(piece_start.numel() >= nnz, "piece_start must hold nnz entries");
   CHK(n_pieces.numel() >= 1 && spill_count.numel() >= 1, "counters");
-  CHK(gw.numel() == nnz && gv.numel() == nnz * K, "gw/gv shape");
   CHK(gradV.numel() == V.numel() && gradW.numel() == W.numel() &&
           nV.numel() == V.numel() && nW.numel() == W.numel() &&
           V.numel() == W.numel() * K,
@@ -268,6 +301,29 @@ void fm_segment_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
     check_cuda_f32(*zV, "zV");
     CHK(zV->numel() == V.numel(), "zV shape");
   }
+}
+
+// Segment backward: one K-lane subgroup per piece of the work list sums the
+// piece's gradients; whole pieces get the optimizer update in place,
+// partial ones go to the slabs and `spill` (fid list + counter, consumed by
+// fm_adagrad_apply / fm_ftrl_apply). opt_mode as in fm_sorted_apply_fused.
+void fm_segment_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
+                      at::Tensor piece_start, at::Tensor n_pieces,
+                      at::Tensor gw, at::Tensor gv, at::Tensor gradW,
+                      at::Tensor gradV, at::Tensor spill,
+                      at::Tensor spill_count, at::Tensor W, at::Tensor V,
+                      at::Tensor nW, at::Tensor nV,
+                      c10::optional<at::Tensor> zW,
+                      c10::optional<at::Tensor> zV, int64_t opt_mode,
+                      double p0, double p1, double p2, double p3, double v_lr,
+                      double v_eps, double v_l2) {
+  check_segment_common(sorted_fids, piece_start, n_pieces, gradW, gradV, spill,
+                       spill_count, W, V, nW, nV, zW, zV, opt_mode);
+  check_cuda_f32(gw, "gw");
+  check_cuda_f32(gv, "gv");
+  const long nnz = sorted_fids.numel();
+  const int K = (int)V.size(1);
+  CHK(gw.numel() == nnz && gv.numel() == nnz * K, "gw/gv shape");
   const int* perm_ptr = nullptr;
   at::Tensor perm_i;
   if (perm.has_value()) {
@@ -280,6 +336,45 @@ void fm_segment_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
   lightctr::fm_segment_apply_launch(
       sorted_fids.data_ptr<int>(), perm_ptr, piece_start.data_ptr<int>(),
       n_pieces.data_ptr<int>(), gw.data_ptr<float>(), gv.data_ptr<float>(),
+      gradW.data_ptr<float>(), gradV.data_ptr<float>(),
+      spill.data_ptr<int>(), spill_count.data_ptr<int>(), (int)spill.numel(),
+      (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), W.data_ptr<float>(),
+      nW.data_ptr<float>(),
+      zW.has_value() ? zW->data_ptr<float>() : nullptr, nV.data_ptr<float>(),
+      zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
+      (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
+      num_cus, cur_stream());
+}
+
+// Segment backward from the sorted records of fm_forward_train: each entry's
+// gradient is recomputed from (row, x), sumVX[row], dpred[row] and the V row
+// its piece loads, so there is no per-entry gradient buffer and no perm.
+void fm_segment_apply_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
+                          at::Tensor sumVX, at::Tensor dpred,
+                          at::Tensor piece_start, at::Tensor n_pieces,
+                          at::Tensor gradW, at::Tensor gradV, at::Tensor spill,
+                          at::Tensor spill_count, at::Tensor W, at::Tensor V,
+                          at::Tensor nW, at::Tensor nV,
+                          c10::optional<at::Tensor> zW,
+                          c10::optional<at::Tensor> zV, int64_t opt_mode,
+                          double p0, double p1, double p2, double p3,
+                          double v_lr, double v_eps, double v_l2) {
+  check_segment_common(sorted_fids, piece_start, n_pieces, gradW, gradV, spill,
+                       spill_count, W, V, nW, nV, zW, zV, opt_mode);
+  const long nnz = sorted_fids.numel();
+  const int K = (int)V.size(1);
+  check_cuda_rec(sorted_rec, nnz, "sorted_rec");
+  check_cuda_f32(sumVX, "sumVX");
+  check_cuda_f32(dpred, "dpred");
+  const long B = dpred.numel();
+  CHK(sumVX.numel() == B * K, "sumVX must be [B, K]");
+  CHK(nnz == 0 || B >= 1, "entries need rows");
+  const int num_cus =
+      at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  lightctr::fm_segment_recompute_launch(
+      sorted_fids.data_ptr<int>(), sorted_rec.data_ptr<int>(),
+      sumVX.data_ptr<float>(), dpred.data_ptr<float>(), (int)B,
+      piece_start.data_ptr<int>(), n_pieces.data_ptr<int>(),
       gradW.data_ptr<float>(), gradV.data_ptr<float>(),
       spill.data_ptr<int>(), spill_count.data_ptr<int>(), (int)spill.numel(),
       (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), W.data_ptr<float>(),
@@ -813,6 +908,28 @@ std::vector<at::Tensor> radix_sort_index(at::Tensor keys, int64_t end_bit) {
   return {sorted, perm};
 }
 
+// The same sort carrying an 8-byte record per key ([n, 2] int32) instead of
+// an index: returns (sorted_keys int32, sorted_rec [n, 2] int32). No iota
+// buffer, no permutation.
+std::vector<at::Tensor> radix_sort_rec(at::Tensor keys, at::Tensor rec,
+                                       int64_t end_bit) {
+  check_cuda_i32(keys, "keys");
+  CHK(end_bit >= 1 && end_bit <= 32, "end_bit in [1,32]");
+  const int n = (int)keys.numel();
+  check_cuda_rec(rec, n, "rec");
+  auto sorted = at::empty_like(keys);
+  auto sorted_rec = at::empty_like(rec);
+  if (n == 0) return {sorted, sorted_rec};
+  const unsigned long bytes =
+      lightctr::radix_sort_pairs_rec_temp_bytes(n, (int)end_bit);
+  auto temp = at::empty({(long)bytes}, keys.options().dtype(at::kByte));
+  lightctr::radix_sort_pairs_rec_launch(
+      temp.data_ptr(), bytes, keys.data_ptr<int>(), sorted.data_ptr<int>(),
+      rec.data_ptr<int>(), sorted_rec.data_ptr<int>(), n, (int)end_bit,
+      cur_stream());
+  return {sorted, sorted_rec};
+}
+
 at::Tensor colsum(at::Tensor dZ) {
   check_cuda_f32(dZ, "dZ");
   const int M = (int)dZ.size(0), N = (int)dZ.size(1);
@@ -1137,6 +1254,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "lightctr_amd HIP kernels (gfx950)";
   m.def("fm_forward", &fm_forward, "FM fused forward (pred, sumVX)");
   m.def("logloss_grad", &logloss_grad, "stable logloss + dpred");
+  m.def("fm_forward_train", &fm_forward_train,
+        "FM training forward -> (loss, dpred, sumVX, rec)",
+        py::arg("row_ptr"), py::arg("fids"), py::arg("vals"), py::arg("W"),
+        py::arg("V"), py::arg("label"), py::arg("scale"));
   m.def("fm_backward", &fm_backward, "FM fused backward scatter");
   m.def("fm_backward_emit", &fm_backward_emit,
         "FM backward phase 1: per-entry grads (no atomics); pos=write slots",
@@ -1170,6 +1291,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("zW"), py::arg("zV"), py::arg("opt_mode"), py::arg("p0"),
         py::arg("p1"), py::arg("p2"), py::arg("p3"), py::arg("v_lr") = 0.05,
         py::arg("v_eps") = 1e-8, py::arg("v_l2") = 1e-5);
+  m.def("fm_segment_apply_rec", &fm_segment_apply_rec,
+        "per-piece segment reduce recomputing the gradients from sorted "
+        "records + fused optimizer; partial pieces spill",
+        py::arg("sorted_fids"), py::arg("sorted_rec"), py::arg("sumVX"),
+        py::arg("dpred"), py::arg("piece_start"), py::arg("n_pieces"),
+        py::arg("gradW"), py::arg("gradV"), py::arg("spill"),
+        py::arg("spill_count"), py::arg("W"), py::arg("V"), py::arg("nW"),
+        py::arg("nV"), py::arg("zW"), py::arg("zV"), py::arg("opt_mode"),
+        py::arg("p0"), py::arg("p1"), py::arg("p2"), py::arg("p3"),
+        py::arg("v_lr") = 0.05, py::arg("v_eps") = 1e-8,
+        py::arg("v_l2") = 1e-5);
   m.def("ffm_forward", &ffm_forward, "FFM pairwise forward (LDS-staged)");
   m.def("ffm_forward_pp", &ffm_forward_pp, "lane-per-pair FFM forward");
   m.def("ffm_row_emit", &ffm_row_emit,
@@ -1240,6 +1372,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("inv_perm_i32", &inv_perm_i32, "inverse permutation (int32)");
   m.def("radix_sort_index", &radix_sort_index,
         "bit-range radix sort -> (sorted, perm)");
+  m.def("radix_sort_rec", &radix_sort_rec,
+        "bit-range radix sort with [n,2] int32 records as payload -> "
+        "(sorted, sorted_rec)",
+        py::arg("keys"), py::arg("rec"), py::arg("end_bit"));
   m.def("colsum", &colsum, "bias gradient column sum");
   m.def("to_bf16", &to_bf16, "f32 -> bf16 convert");
   m.def("dense_adam", &dense_adam, "dense Adam + bf16 mirror refresh");

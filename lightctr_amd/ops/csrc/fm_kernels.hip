@@ -111,22 +111,33 @@ __device__ __forceinline__ void fm_opt_step_w(int opt_mode, float& w,
   }
 }
 
+// Stable logloss + upstream gradient of one row: the one place this maths
+// lives (logloss_grad_kernel and the training forward both call it).
+//   loss  = max(z,0) - z*y + log(1+exp(-|z|))
+//   dpred = (sigmoid(z) - y) * scale
+__device__ __forceinline__ void logloss_grad_row(float z, float y, float scale,
+                                                 float& loss, float& dpred) {
+  loss = fmaxf(z, 0.f) - z * y + __logf(1.f + __expf(-fabsf(z)));
+  dpred = (sigmoidf_clamped(z) - y) * scale;
+}
+
 // ---------------------------------------------------------------------------
 // Forward: pred[row] = sum_j w[fid]*x + 0.5*(||sumVX||^2 - sum_j ||v*x||^2)
 // Also writes sumVX[row*K+k] (needed by backward).
 // ---------------------------------------------------------------------------
-template <int K>
-__global__ void fm_forward_kernel(const int* __restrict__ row_ptr,
-                                  const int* __restrict__ fids,
-                                  const float* __restrict__ vals,
-                                  const float* __restrict__ W,
-                                  const float* __restrict__ V,
-                                  float* __restrict__ pred,
-                                  float* __restrict__ sumVX, int B) {
+// Row body shared by the inference and the training forward. TRAIN adds the
+// per-entry record rec[j] = {row, bits of vals[j]} (written by the k == 0
+// lane of the feature group that has just loaded vals[j]): the segment
+// backward sorts these records by fid and recomputes each entry's gradient
+// from them, so no per-entry gradient buffer is ever written.
+// Returns the row's pred (valid in every lane).
+template <int K, bool TRAIN>
+__device__ __forceinline__ float fm_forward_row(
+    const int* __restrict__ row_ptr, const int* __restrict__ fids,
+    const float* __restrict__ vals, const float* __restrict__ W,
+    const float* __restrict__ V, float* __restrict__ sumVX,
+    int2* __restrict__ rec, int row, int lane) {
   constexpr int G = LCTR_WAVE / K;  // features processed in parallel
-  const int lane = threadIdx.x & (LCTR_WAVE - 1);
-  const int row = blockIdx.x * (blockDim.x / LCTR_WAVE) + (threadIdx.x >> 6);
-  if (row >= B) return;
   const int g = lane / K;
   const int k = lane % K;
   const int beg = row_ptr[row], end = row_ptr[row + 1];
@@ -151,6 +162,8 @@ __global__ void fm_forward_kernel(const int* __restrict__ row_ptr,
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
+      if (TRAIN && k == 0)
+        rec[j + u * G] = make_int2(row, __float_as_int(x[u]));
       const float vx = v[u] * x[u];
       sVX += vx;
       sV2X2 += vx * vx;
@@ -160,6 +173,7 @@ __global__ void fm_forward_kernel(const int* __restrict__ row_ptr,
   for (; j < end; j += G) {
     const int fid = fids[j];
     const float x = vals[j];
+    if (TRAIN && k == 0) rec[j] = make_int2(row, __float_as_int(x));
     const float vx = V[(size_t)fid * K + k] * x;
     sVX += vx;
     sV2X2 += vx * vx;
@@ -173,7 +187,46 @@ __global__ void fm_forward_kernel(const int* __restrict__ row_ptr,
   const float tot_v2 = wave_reduce_sum(sV2X2);
   const float tot_lin = wave_reduce_sum(lin);
   if (lane < K) sumVX[(size_t)row * K + lane] = sVX;
-  if (lane == 0) pred[row] = tot_lin + 0.5f * (tot_t - tot_v2);
+  return tot_lin + 0.5f * (tot_t - tot_v2);
+}
+
+template <int K>
+__global__ void fm_forward_kernel(const int* __restrict__ row_ptr,
+                                  const int* __restrict__ fids,
+                                  const float* __restrict__ vals,
+                                  const float* __restrict__ W,
+                                  const float* __restrict__ V,
+                                  float* __restrict__ pred,
+                                  float* __restrict__ sumVX, int B) {
+  const int lane = threadIdx.x & (LCTR_WAVE - 1);
+  const int row = blockIdx.x * (blockDim.x / LCTR_WAVE) + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const float p = fm_forward_row<K, false>(row_ptr, fids, vals, W, V, sumVX,
+                                           nullptr, row, lane);
+  if (lane == 0) pred[row] = p;
+}
+
+// Training forward: the row body above plus, in lane 0, the loss and the
+// upstream gradient of the row (what logloss_grad_kernel computes from a
+// stored pred), and the per-entry records for the segment backward.
+template <int K>
+__global__ void fm_forward_train_kernel(
+    const int* __restrict__ row_ptr, const int* __restrict__ fids,
+    const float* __restrict__ vals, const float* __restrict__ W,
+    const float* __restrict__ V, const float* __restrict__ label, float scale,
+    float* __restrict__ loss, float* __restrict__ dpred,
+    float* __restrict__ sumVX, int2* __restrict__ rec, int B) {
+  const int lane = threadIdx.x & (LCTR_WAVE - 1);
+  const int row = blockIdx.x * (blockDim.x / LCTR_WAVE) + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const float p = fm_forward_row<K, true>(row_ptr, fids, vals, W, V, sumVX,
+                                          rec, row, lane);
+  if (lane == 0) {
+    float l, d;
+    logloss_grad_row(p, label[row], scale, l, d);
+    loss[row] = l;
+    dpred[row] = d;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -189,11 +242,10 @@ __global__ void logloss_grad_kernel(const float* __restrict__ pred,
                                     int B) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  const float z = pred[i];
-  const float y = label[i];
-  // loss = max(z,0) - z*y + log(1+exp(-|z|))  (stable logloss)
-  loss[i] = fmaxf(z, 0.f) - z * y + __logf(1.f + __expf(-fabsf(z)));
-  dpred[i] = (sigmoidf_clamped(z) - y) * scale;
+  float l, d;
+  logloss_grad_row(pred[i], label[i], scale, l, d);
+  loss[i] = l;
+  dpred[i] = d;
 }
 
 // ---------------------------------------------------------------------------
@@ -658,18 +710,85 @@ __global__ void fm_segscan4_apply_kernel(
 //     kernels below consume, re-zeroing the slab entries they read.
 // At most ceil(nnz/CAP)-1 runs cross a boundary, which bounds the list.
 // The grid is fixed; waves stride over the device-side piece count. Per
-// piece the dependent loads are piece_start -> (fid, perm) -> (gv, V, nV,
-// neighbours): the first two levels are fetched one and two iterations
-// ahead, so an iteration waits for one round trip, not three.
+// piece the dependent loads are piece_start -> (fid, handle) -> (entry data,
+// V, nV, neighbours): the first two levels are fetched one and two
+// iterations ahead, so an iteration waits for one round trip, not three.
+//
+// Where an entry's gradient comes from is a policy (Src), so the piece loop,
+// the whole/partial logic, the spill append and the optimizer calls exist
+// once. A policy has
+//   Handle             what is read sequentially at sorted position e, one
+//                      batch ahead (handle(e)); Handle{} stands for no entry
+//   Data load<K>(h,k)  the entry's random gather(s), issued per batch
+//   add(h,t,v,acc,accw) the entry's contribution, v = the piece's V[fid,k]
+//                      from before the update; Handle{} with Data{} adds 0
 // ---------------------------------------------------------------------------
-template <int K>
+// Gathered: the gradients were emitted per entry (fm_backward_emit_kernel)
+// in CSR order; handle = perm[e], the entry's slot in gv / gw.
+struct FmSrcGathered {
+  const int* __restrict__ perm;
+  const float* __restrict__ gw;
+  const float* __restrict__ gv;
+  using Handle = int;
+  struct Data {
+    float gv, gw;
+  };
+  __device__ __forceinline__ Handle handle(int e) const {
+    return perm ? perm[e] : e;
+  }
+  template <int K>
+  __device__ __forceinline__ Data load(Handle h, int k) const {
+    return {gv[(size_t)h * K + k], (k == 0) ? gw[h] : 0.f};
+  }
+  __device__ __forceinline__ void add(Handle, Data t, float, float& acc,
+                                      float& accw) const {
+    acc += t.gv;
+    accw += t.gw;
+  }
+};
+
+// Recompute: the sort carried the forward's records {row, bits of x} as its
+// payload, so position e holds the entry's row and value directly (no perm,
+// no per-entry gradient buffer). The gathers go to sumVX (B*K floats, a few
+// MB) and dpred; the contribution is formed with the expressions of
+// fm_backward_emit_kernel, per entry (not factorised over the piece), from
+// the V row the piece loads for the optimizer anyway.
+struct FmSrcRecompute {
+  const int2* __restrict__ rec;
+  const float* __restrict__ sumVX;
+  const float* __restrict__ dpred;
+  int B;
+  using Handle = int2;
+  struct Data {
+    float sv, d;
+  };
+  __device__ __forceinline__ Handle handle(int e) const { return rec[e]; }
+  template <int K>
+  __device__ __forceinline__ Data load(Handle h, int k) const {
+    // rows come from the forward kernel; the clamp only keeps a foreign
+    // record buffer from reading outside sumVX / dpred
+    const int row = min(max(h.x, 0), B - 1);
+    return {sumVX[(size_t)row * K + k], dpred[row]};
+  }
+  __device__ __forceinline__ void add(Handle h, Data t, float v, float& acc,
+                                      float& accw) const {
+    const float x = __int_as_float(h.y);
+    acc += t.d * (t.sv - v * x) * x;
+    accw += t.d * x;
+  }
+};
+
+// D: entries per batch of the inner loop (independent gathers in flight per
+// lane). More lookahead costs registers, i.e. resident waves.
+template <int K, class Src, int D>
 __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
-    const int* __restrict__ sorted_fids, const int* __restrict__ perm,
+    const int* __restrict__ sorted_fids, Src src,
     const int* __restrict__ piece_start, const int* __restrict__ n_pieces,
-    const float* __restrict__ gw, const float* __restrict__ gv,
     float* __restrict__ gradW, float* __restrict__ gradV,
     int* __restrict__ spill, int* __restrict__ spill_count, int spill_cap,
     int nnz, int opt_mode, float* __restrict__ V, FmOptArgs oa) {
+  using Handle = typename Src::Handle;
+  using Data = typename Src::Data;
   constexpr int G = LCTR_WAVE / K;
   const int lane = threadIdx.x & (LCTR_WAVE - 1);
   const int g = lane / K;
@@ -690,37 +809,36 @@ __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
       if (p + 1 < P) e = min(max(piece_start[p + 1], s), nnz);
     }
   };
-  auto load_head = [&](int s, int& fid, long& src) {
+  auto load_head = [&](int s, int& fid, Handle& h) {
     fid = -1;
-    src = 0;
+    h = Handle{};
     if (s < nnz) {
       fid = sorted_fids[s];
-      src = perm ? (long)perm[s] : (long)s;
+      h = src.handle(s);
     }
   };
 
   int s0, e0, s1, e1, fid0;
-  long src0;
+  Handle h0;
   load_piece(base, s0, e0);
   load_piece(base + stride, s1, e1);
-  load_head(s0, fid0, src0);
+  load_head(s0, fid0, h0);
 
   // wave-uniform loop: every lane stays in it until the wave's last group,
   // so the ballot below sees the whole wave
   for (; base < P; base += stride) {
     int s2, e2, fid1;
-    long src1;
+    Handle h1;
     load_piece(base + 2 * stride, s2, e2);
-    load_head(s1, fid1, src1);
+    load_head(s1, fid1, h1);
 
     bool spill_me = false;
     if (s0 < nnz) {
       const int fid = fid0;
       const size_t off = (size_t)fid * K + k;
       // everything the piece needs besides its own entries depends on fid
-      // alone: issue it with the first gradient row
-      float acc = gv[(size_t)src0 * K + k];
-      float accw = (k == 0) ? gw[src0] : 0.f;
+      // alone: issue it with the first entry's data
+      const Data t0 = src.template load<K>(h0, k);
       const bool head = (s0 == 0) || (sorted_fids[s0 - 1] != fid);
       const bool tail = (e0 >= nnz) || (sorted_fids[e0] != fid);
       float v = V[off], n = oa.nV[off];
@@ -731,37 +849,36 @@ __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
         nw = oa.nW[fid];
         if (opt_mode != 1) zw = oa.zW[fid];
       }
-      // rest of the piece, 8 independent row loads per batch; the batch's
-      // source slots (perm) are fetched one batch ahead, so a batch costs
-      // one round trip, not perm -> gv
-      int src[8];
+      // rest of the piece, D independent gathers per batch; the batch's
+      // handles are fetched one batch ahead, so a batch costs one round
+      // trip, not handle -> data
+      Handle hn[D];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
+      for (int u = 0; u < D; ++u) {
         const int ee = s0 + 1 + u;
-        src[u] = (perm && ee < e0) ? perm[ee] : ee;
+        hn[u] = (ee < e0) ? src.handle(ee) : Handle{};
       }
-      for (int e = s0 + 1; e < e0; e += 8) {
-        float tv[8], tw[8];
+      float acc = 0.f, accw = 0.f;
+      for (int e = s0 + 1; e < e0; e += D) {
+        Handle hc[D];
+        Data t[D];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          tv[u] = 0.f;
-          tw[u] = 0.f;
-          if (e + u < e0) {
-            tv[u] = gv[(size_t)src[u] * K + k];
-            if (k == 0) tw[u] = gw[src[u]];
-          }
+        for (int u = 0; u < D; ++u) {
+          hc[u] = hn[u];
+          t[u] = Data{};
+          if (e + u < e0) t[u] = src.template load<K>(hc[u], k);
         }
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int ee = e + 8 + u;
-          src[u] = (perm && ee < e0) ? perm[ee] : ee;
+        for (int u = 0; u < D; ++u) {
+          const int ee = e + D + u;
+          hn[u] = (ee < e0) ? src.handle(ee) : Handle{};
         }
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          acc += tv[u];
-          accw += tw[u];
-        }
+        for (int u = 0; u < D; ++u) src.add(hc[u], t[u], v, acc, accw);
       }
+      // the head entry last: its add is the first use of v, so the first
+      // batch's gathers are issued without waiting for the V row
+      src.add(h0, t0, v, acc, accw);
       if (head && tail) {
         fm_opt_step_v(opt_mode, v, n, z, acc, oa);
         if (opt_mode == 2) oa.zV[off] = z;
@@ -791,7 +908,7 @@ __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
     s0 = s1;
     e0 = e1;
     fid0 = fid1;
-    src0 = src1;
+    h0 = h1;
     s1 = s2;
     e1 = e2;
   }
@@ -918,6 +1035,20 @@ void fm_forward_launch(const int* row_ptr, const int* fids, const float* vals,
   DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_kernel<KC>), grid, block, 0,
                                    stream, row_ptr, fids, vals, W, V, pred,
                                    sumVX, B));
+}
+
+void fm_forward_train_launch(const int* row_ptr, const int* fids,
+                             const float* vals, const float* W, const float* V,
+                             const float* label, float scale, float* loss,
+                             float* dpred, float* sumVX, int* rec, int B,
+                             int K, hipStream_t stream) {
+  if (B <= 0) return;
+  const int wpb = waves_per_block();
+  dim3 block(wpb * LCTR_WAVE);
+  dim3 grid((B + wpb - 1) / wpb);
+  DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_train_kernel<KC>), grid, block,
+                                   0, stream, row_ptr, fids, vals, W, V, label,
+                                   scale, loss, dpred, sumVX, (int2*)rec, B));
 }
 
 void logloss_grad_launch(const float* pred, const float* label, float* loss,
@@ -1050,15 +1181,50 @@ void fm_sorted_apply_launch(const int* sorted_fids, const int* perm,
 }
 
 // resident 256-thread blocks of the segment kernel per CU (register bound)
-template <int K>
+template <int K, class Src, int D>
 static int fm_segment_blocks_per_cu() {
   static const int nb = [] {
     int n = 0;
     LCTR_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &n, fm_segment_apply_kernel<K>, waves_per_block() * LCTR_WAVE, 0));
+        &n, fm_segment_apply_kernel<K, Src, D>,
+        waves_per_block() * LCTR_WAVE, 0));
     return std::max(n, 1);
   }();
   return nb;
+}
+
+// What both entry sources share besides the policy object
+struct FmSegmentArgs {
+  const int* sorted_fids;
+  const int* piece_start;
+  const int* n_pieces;
+  float* gradW;
+  float* gradV;
+  int* spill;
+  int* spill_count;
+  int spill_cap, nnz, opt_mode;
+  float* V;
+  FmOptArgs oa;
+  int num_cus;
+};
+
+template <int K, class Src, int D>
+static void fm_segment_launch_one(const FmSegmentArgs& a, const Src& src,
+                                  hipStream_t stream) {
+  // fixed grid: exactly the blocks the device holds at once (a block more
+  // per CU would run as a second round), never more than one subgroup per
+  // possible piece
+  const int wpb = waves_per_block();
+  constexpr int G = LCTR_WAVE / K;
+  const int per_cu = fm_segment_blocks_per_cu<K, Src, D>();
+  const long need = ((long)a.nnz + (long)wpb * G - 1) / ((long)wpb * G);
+  const int blocks = (int)std::max(
+      1L, std::min(need, (long)per_cu * std::max(a.num_cus, 1)));
+  hipLaunchKernelGGL((fm_segment_apply_kernel<K, Src, D>), dim3(blocks),
+                     dim3(wpb * LCTR_WAVE), 0, stream, a.sorted_fids, src,
+                     a.piece_start, a.n_pieces, a.gradW, a.gradV, a.spill,
+                     a.spill_count, a.spill_cap, a.nnz, a.opt_mode, a.V,
+                     a.oa);
 }
 
 void fm_segment_apply_launch(const int* sorted_fids, const int* perm,
@@ -1071,23 +1237,36 @@ void fm_segment_apply_launch(const int* sorted_fids, const int* perm,
                              float p2, float p3, float q0, float q1, float q2,
                              int num_cus, hipStream_t stream) {
   if (nnz <= 0) return;
-  // fixed grid: exactly the blocks the device holds at once (a block more
-  // per CU would run as a second round), never more than one subgroup per
-  // possible piece
-  const int wpb = waves_per_block();
-  const int G = LCTR_WAVE / K;
-  int per_cu = 1;
-  DISPATCH_K(K, per_cu = fm_segment_blocks_per_cu<KC>());
-  const long need = ((long)nnz + (long)wpb * G - 1) / ((long)wpb * G);
-  const int blocks =
-      (int)std::max(1L, std::min(need, (long)per_cu * std::max(num_cus, 1)));
-  FmOptArgs oa{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1, q2};
-  DISPATCH_K(K, hipLaunchKernelGGL((fm_segment_apply_kernel<KC>),
-                                   dim3(blocks), dim3(wpb * LCTR_WAVE), 0,
-                                   stream, sorted_fids, perm, piece_start,
-                                   n_pieces, gw, gv, gradW, gradV, spill,
-                                   spill_count, spill_cap, nnz, opt_mode, V,
-                                   oa));
+  const FmSegmentArgs a{sorted_fids, piece_start, n_pieces, gradW, gradV,
+                        spill, spill_count, spill_cap, nnz, opt_mode, V,
+                        FmOptArgs{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1,
+                                  q2},
+                        num_cus};
+  const FmSrcGathered src{perm, gw, gv};
+  DISPATCH_K(K, (fm_segment_launch_one<KC, FmSrcGathered, 8>(a, src, stream)));
+}
+
+// Batch depth of the recompute reduce. Measured at the flagship shape: 4
+// (65 VGPR, 7 waves/SIMD) beats 8 (85 VGPR, 5 waves/SIMD) by 3.7 % of the
+// step; 8 wins only above CAP 512 (profiles/r4_01_fm_recompute.txt).
+constexpr int kFmRecomputeDepth = 4;
+
+void fm_segment_recompute_launch(
+    const int* sorted_fids, const int* rec, const float* sumVX,
+    const float* dpred, int B, const int* piece_start, const int* n_pieces,
+    float* gradW, float* gradV, int* spill, int* spill_count, int spill_cap,
+    int nnz, int K, int opt_mode, float* V, float* W, float* nW, float* zW,
+    float* nV, float* zV, float p0, float p1, float p2, float p3, float q0,
+    float q1, float q2, int num_cus, hipStream_t stream) {
+  if (nnz <= 0 || B <= 0) return;
+  const FmSegmentArgs a{sorted_fids, piece_start, n_pieces, gradW, gradV,
+                        spill, spill_count, spill_cap, nnz, opt_mode, V,
+                        FmOptArgs{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1,
+                                  q2},
+                        num_cus};
+  const FmSrcRecompute src{(const int2*)rec, sumVX, dpred, B};
+  DISPATCH_K(K, (fm_segment_launch_one<KC, FmSrcRecompute, kFmRecomputeDepth>(
+                    a, src, stream)));
 }
 
 void bitmap_compact_launch(unsigned long long* bitmap, int nwords,

@@ -41,6 +41,19 @@ void fm_segment_apply_launch(const int* sorted_fids, const int* perm,
                              float* nV, float* zV, float p0, float p1,
                              float p2, float p3, float q0, float q1, float q2,
                              int num_cus, ihipStream_t* stream);
+// rec: [n, 2] int32 records {row, bits of x}, 8-byte aligned
+void fm_forward_train_launch(const int* row_ptr, const int* fids,
+                             const float* vals, const float* W, const float* V,
+                             const float* label, float scale, float* loss,
+                             float* dpred, float* sumVX, int* rec, int B,
+                             int K, ihipStream_t* stream);
+void fm_segment_recompute_launch(
+    const int* sorted_fids, const int* rec, const float* sumVX,
+    const float* dpred, int B, const int* piece_start, const int* n_pieces,
+    float* gradW, float* gradV, int* spill, int* spill_count, int spill_cap,
+    int nnz, int K, int opt_mode, float* V, float* W, float* nW, float* zW,
+    float* nV, float* zV, float p0, float p1, float p2, float p3, float q0,
+    float q1, float q2, int num_cus, ihipStream_t* stream);
 void bitmap_compact_launch(unsigned long long* bitmap, int nwords,
                            int* out_fids, int* out_count, int cap,
                            ihipStream_t* stream);
@@ -247,6 +260,12 @@ unsigned long radix_sort_pairs_i32_temp_bytes(int n, int end_bit);
 void radix_sort_pairs_i32_launch(void* temp, unsigned long temp_bytes,
                                  const int* keys_in, int* keys_out,
                                  const int* vals_in, int* vals_out, int n,
+                                 int end_bit, ihipStream_t* stream);
+// 8-byte payload: rec_in / rec_out are [n, 2] int32, 8-byte aligned
+unsigned long radix_sort_pairs_rec_temp_bytes(int n, int end_bit);
+void radix_sort_pairs_rec_launch(void* temp, unsigned long temp_bytes,
+                                 const int* keys_in, int* keys_out,
+                                 const int* rec_in, int* rec_out, int n,
                                  int end_bit, ihipStream_t* stream);
 // work list of the segment backward: compacted piece starts of a sorted
 // stream + their count (device side); zero_me (optional) is reset to 0

@@ -60,6 +60,30 @@ void radix_sort_pairs_i32_launch(void* temp, size_t temp_bytes,
                                            stream, false));
 }
 
+// Same sort with an 8-byte payload: the FM training forward writes one
+// record {row, bits of x} per entry, and the segment backward reads the
+// sorted records in place of a permutation. The payload is handed over as a
+// pointer, so no iota fill and no temp-storage copy of the inputs.
+using SortRec = unsigned long long;
+
+size_t radix_sort_pairs_rec_temp_bytes(int n, int end_bit) {
+  size_t bytes = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, bytes, (const int*)nullptr,
+                                  (int*)nullptr, (const SortRec*)nullptr,
+                                  (SortRec*)nullptr, (size_t)n, 0u,
+                                  (unsigned)end_bit, (hipStream_t)0, false);
+  return bytes;
+}
+
+void radix_sort_pairs_rec_launch(void* temp, size_t temp_bytes,
+                                 const int* keys_in, int* keys_out,
+                                 const int* rec_in, int* rec_out, int n,
+                                 int end_bit, hipStream_t stream) {
+  LCTR_CHECK_HIP(rocprim::radix_sort_pairs(
+      temp, temp_bytes, keys_in, keys_out, (const SortRec*)rec_in,
+      (SortRec*)rec_out, (size_t)n, 0u, (unsigned)end_bit, stream, false));
+}
+
 // ---------------------------------------------------------------------------
 // Work list of the segment backward (fm_kernels.hip,
 // fm_segment_apply_kernel). Entry e of the sorted stream starts a piece if

@@ -130,15 +130,18 @@ def main():
         print(f"step sorted fused={int(fused)}  {tt:8.1f} us  "
               f"({65536 / tt:.1f}M ex/s)")
         del mm
-    # ... vs the segment mode at each CAP (eager launches, no hipGraph)
-    for cap in (32, 64, 128, 256, 512):
-        mm = FMModel(h, device="cuda")
-        mm.backward_mode = "segment"
-        mm.segment_cap = cap
-        tt = t(lambda: mm.train_step(row_ptr, fids, vals, labels))
-        print(f"step segment cap={cap:4d}  {tt:8.1f} us  "
-              f"({65536 / tt:.1f}M ex/s)")
-        del mm
+    # ... vs the segment modes at each CAP (eager launches, no hipGraph):
+    # "segment" recomputes the gradients from sorted records, "segment_emit"
+    # is the emit-fed reduce timed above
+    for mode in ("segment_emit", "segment"):
+        for cap in (32, 64, 128, 256, 512):
+            mm = FMModel(h, device="cuda")
+            mm.backward_mode = mode
+            mm.segment_cap = cap
+            tt = t(lambda: mm.train_step(row_ptr, fids, vals, labels))
+            print(f"step {mode:12s} cap={cap:4d}  {tt:8.1f} us  "
+                  f"({65536 / tt:.1f}M ex/s)")
+            del mm
 
 
 if __name__ == "__main__":
