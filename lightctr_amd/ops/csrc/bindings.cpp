@@ -27,6 +27,13 @@ void check_cuda_i32(const at::Tensor& t, const char* name) {
   CHK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// the embedding/NFM launchers dispatch K over this set and abort() the
+// process on anything else; reject it here as an exception instead
+void check_embed_k(int64_t K) {
+  CHK(K == 4 || K == 8 || K == 16 || K == 32 || K == 64,
+      "latent width K must be one of 4, 8, 16, 32, 64, got ", K);
+}
+
 ihipStream_t* cur_stream() {
   return (ihipStream_t*)at::cuda::getCurrentCUDAStream().stream();
 }
@@ -983,9 +990,16 @@ void dense_adagrad(at::Tensor W, at::Tensor grad, at::Tensor n,
 at::Tensor embed_gather(at::Tensor row_ptr, at::Tensor fids, at::Tensor vals,
                         at::Tensor E, int64_t nf) {
   check_cuda_i32(row_ptr, "row_ptr");
+  check_cuda_i32(fids, "fids");
+  check_cuda_f32(vals, "vals");
   check_cuda_f32(E, "E");
+  CHK(E.dim() == 2, "E must be [F, K]");
+  CHK(fids.numel() == vals.numel(), "fids/vals length mismatch");
+  CHK(row_ptr.numel() >= 1, "row_ptr must hold B+1 offsets");
+  CHK(nf >= 1, "nf must be >= 1");
   const int B = (int)row_ptr.numel() - 1;
   const int K = (int)E.size(1);
+  check_embed_k(K);
   auto out = at::empty({B, nf * K}, E.options().dtype(at::kBFloat16));
   lightctr::embed_gather_launch(row_ptr.data_ptr<int>(), fids.data_ptr<int>(),
                                 vals.data_ptr<float>(), E.data_ptr<float>(),
@@ -999,7 +1013,12 @@ std::vector<at::Tensor> embed_backward_emit(at::Tensor row_ptr,
                                             int64_t K) {
   check_cuda_i32(row_ptr, "row_ptr");
   check_cuda_f32(dOut, "dOut");
+  check_cuda_f32(vals, "vals");
+  check_cuda_f32(dwide, "dwide");
+  check_embed_k(K);
+  CHK(nf >= 1, "nf must be >= 1");
   const int B = (int)row_ptr.numel() - 1;
+  CHK(dOut.numel() == (int64_t)B * nf * K, "dOut must be [B, nf*K]");
   const auto nnz = vals.numel();
   auto gv = at::empty({nnz, K}, dOut.options());
   auto gw = at::empty({nnz}, dOut.options());
@@ -1048,6 +1067,7 @@ std::vector<at::Tensor> nfm_forward(at::Tensor row_ptr, at::Tensor fids,
   check_cuda_f32(V, "V");
   const int B = (int)row_ptr.numel() - 1;
   const int K = (int)V.size(1);
+  check_embed_k(K);
   auto wide = at::empty({B}, W.options());
   auto sumVX = at::empty({B, K}, V.options());
   auto vec = at::empty({B, K}, V.options());
@@ -1067,6 +1087,7 @@ std::vector<at::Tensor> nfm_backward_emit(at::Tensor row_ptr, at::Tensor fids,
   check_cuda_i32(row_ptr, "row_ptr");
   const int B = (int)row_ptr.numel() - 1;
   const int K = (int)V.size(1);
+  check_embed_k(K);
   const auto nnz = fids.numel();
   auto gw = at::empty({nnz}, V.options());
   auto gv = at::empty({nnz, K}, V.options());

@@ -14,6 +14,8 @@ namespace lightctr {
 // Gather embeddings concatenated by position-in-row (fixed nnz/row layouts,
 // e.g. Criteo 39 fields): out[row, pos*K+k] = E[fid]*x, emitted bf16 for the
 // MLP GEMM (+optional fp32 copy). Wave per row, (pos-group, k) lanes.
+// Positions len(row) <= pos < nf are written as zero; entries past nf are
+// ignored.
 // 8-wave/SIMD cap: the gather allocated 66 VGPR, two registers over
 // the 8-wave boundary (512/8 = 64); the cap re-allocates to 64 with no
 // spill (same lever as the FM walk's WPE=6 — profiles/r2_13_fm_wpe.txt)
@@ -57,6 +59,13 @@ __global__ __launch_bounds__(256, 8) void embed_gather_kernel(
     const float v = E[(size_t)fids[j] * K + k] * vals[j];
     out_bf[((size_t)row * nf + pos) * K + k] = (__bf16)v;
   }
+  // rows shorter than nf (libffm rows with missing fields): zero-pad the
+  // rest of the slice like the CPU gather does; the output is at::empty.
+  // The unwritten tail [(lim-beg)*K, nf*K) is contiguous, so the wave
+  // lane-strides it. No trip for fixed-width rows.
+  __bf16* tail = out_bf + (size_t)row * nf * K;
+  for (int i = max(lim - beg, 0) * K + lane; i < nf * K; i += LCTR_WAVE)
+    tail[i] = (__bf16)0.f;
 }
 
 // Backward emit for the gather: gv[j,k] = dOut[row, pos*K+k] * x_j and

@@ -353,7 +353,11 @@ def test_gemm_degenerate_shapes():
     assert torch.allclose(dW, ref, atol=2e-1, rtol=1e-2), \
         (dW - ref).abs().max()
 
-    # small-output wgrad: dW[64,16] = dZ[B,64]^T @ X[B,16], deep K
+    # small-output wgrad: dW[64,16] = dZ[B,64]^T @ X[B,16], deep K. Both
+    # dims are multiples of 16, so gemm_wgrad_eligible takes this shape and
+    # it runs on the wgrad128 kernel, not on small_wgrad_kernel; the
+    # shapes that reach small_wgrad_kernel (M or N not 16-aligned) are in
+    # test_nn_elementwise_gpu.py::test_small_wgrad_kernel_is_reached
     B2 = 16384
     dZ2 = (torch.randn(B2, 64, generator=g) * 0.1).to(torch.bfloat16).cuda()
     X2 = (torch.randn(B2, 16, generator=g) * 0.5).to(torch.bfloat16).cuda()
