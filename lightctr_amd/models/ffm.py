@@ -102,7 +102,15 @@ class FFMModel:
         self.fused_apply = True
         self._fields_checked = False
         if self._use_hip:
-            require_hip_ops()
+            ops = require_hip_ops()
+            # the sorted walk keeps one [nf, K+1] fp32 block per wave in
+            # LDS; a pair past the device's per-block limit cannot launch
+            need = ops.ffm_block_lds_bytes(nf, K)
+            have = ops.ffm_max_lds_per_block()
+            if not self._rowemit_ok and need > have:
+                raise ValueError(
+                    f"num_fields={nf}, k={K}: the sorted FFM backward needs "
+                    f"{need} bytes of LDS per block, the device gives {have}")
 
     @property
     def _Vc(self):

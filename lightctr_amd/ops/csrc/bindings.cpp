@@ -2,6 +2,7 @@
 // the native data loader. Host-only translation unit.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <c10/cuda/CUDAException.h>
 
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +33,22 @@ void check_cuda_i32(const at::Tensor& t, const char* name) {
 void check_embed_k(int64_t K) {
   CHK(K == 4 || K == 8 || K == 16 || K == 32 || K == 64,
       "latent width K must be one of 4, 8, 16, 32, 64, got ", K);
+}
+
+// the FFM launchers dispatch K over the same set and abort() likewise
+void check_ffm_v(const at::Tensor& V) {
+  CHK(V.dim() == 3, "V must be [F, nfields, K]");
+  check_embed_k(V.size(2));
+}
+
+// ffm_sorted_backward / ffm_block_emit keep one [nfields, K+1] fp32 block
+// per wave in dynamic LDS; a request past the per-block limit is a launch
+// error that would leave the gradients unwritten
+void check_ffm_block_lds(int nfields, int K, const char* op) {
+  const long need = lightctr::ffm_block_lds_bytes(nfields, K);
+  const long have = lightctr::ffm_max_lds_per_block();
+  CHK(need <= have, op, ": nfields=", nfields, ", K=", K, " needs ", need,
+      " bytes of LDS per block, the device gives ", have);
 }
 
 ihipStream_t* cur_stream() {
@@ -402,6 +419,7 @@ at::Tensor ffm_forward(at::Tensor row_ptr, at::Tensor fields, at::Tensor fids,
   const bool v_bf16 = V.scalar_type() == at::kBFloat16;
   CHK(v_bf16 || V.scalar_type() == at::kFloat, "V must be fp32 or bf16");
   const int B = (int)row_ptr.numel() - 1;
+  check_ffm_v(V);
   const int nfields = (int)V.size(1);
   const int K = (int)V.size(2);
   auto pred = at::empty({B}, W.options());
@@ -423,6 +441,7 @@ at::Tensor ffm_forward_pp(at::Tensor row_ptr, at::Tensor fields,
                           at::Tensor V) {
   check_cuda_i32(row_ptr, "row_ptr");
   const int B = (int)row_ptr.numel() - 1;
+  check_ffm_v(V);
   const int nfields = (int)V.size(1);
   const int K = (int)V.size(2);
   auto pred = at::empty({B}, W.options());
@@ -445,6 +464,7 @@ std::vector<at::Tensor> ffm_row_emit(at::Tensor row_ptr, at::Tensor fields,
   const bool v_bf16 = V.scalar_type() == at::kBFloat16;
   CHK(v_bf16 || V.scalar_type() == at::kFloat, "V must be fp32 or bf16");
   const int B = (int)row_ptr.numel() - 1;
+  check_ffm_v(V);
   const int nfields = (int)V.size(1);
   const int K = (int)V.size(2);
   const int maxn = 40;
@@ -483,7 +503,12 @@ void ffm_blocks_apply_f16(at::Tensor sorted_fids, at::Tensor perm,
     CHK(V && W && nW && nV, "fused apply needs V/W/nW/nV");
     if (opt_mode == 3) CHK(zW.has_value(), "opt_mode 3 needs zW");
   }
+  CHK(gradV.dim() == 2 && gblocks.dim() == 2, "gradV and gblocks must be 2-d");
   const int D = (int)gradV.size(1);
+  CHK(gblocks.size(1) == gradV.size(1), "gblocks width ", gblocks.size(1),
+      " differs from gradV width ", gradV.size(1));
+  CHK(D % 4 == 0 && D <= 1024, "ffm_blocks_apply_f16: D=", D,
+      " unsupported (needs D % 4 == 0 and D <= 1024)");
   lightctr::ffm_blocks_apply_f16_launch(
       sorted_fids.data_ptr<int>(), perm_i.data_ptr<int>(), gblocks.data_ptr(),
       gw.data_ptr<float>(), gradW.data_ptr<float>(), gradV.data_ptr<float>(),
@@ -503,6 +528,7 @@ void ffm_backward(at::Tensor row_ptr, at::Tensor fields, at::Tensor fids,
                   at::Tensor gradW, at::Tensor gradV, at::Tensor touched) {
   check_cuda_i32(row_ptr, "row_ptr");
   const int B = (int)row_ptr.numel() - 1;
+  check_ffm_v(V);
   const int nfields = (int)V.size(1);
   const int K = (int)V.size(2);
   lightctr::ffm_backward_launch(
@@ -520,8 +546,10 @@ void ffm_sorted_backward(at::Tensor sorted_fids, at::Tensor perm,
   check_cuda_i32(sorted_fids, "sorted_fids");
   auto perm_i = perm32(perm).contiguous();
   check_cuda_i32(row_of_entry, "row_of_entry");
+  check_ffm_v(V);
   const int nfields = (int)V.size(1);
   const int K = (int)V.size(2);
+  check_ffm_block_lds(nfields, K, "ffm_sorted_backward");
   lightctr::ffm_sorted_backward_launch(
       sorted_fids.data_ptr<int>(), perm_i.data_ptr<int>(),
       row_of_entry.data_ptr<int>(), row_ptr.data_ptr<int>(),
@@ -529,6 +557,7 @@ void ffm_sorted_backward(at::Tensor sorted_fids, at::Tensor perm,
       V.data_ptr<float>(), dpred.data_ptr<float>(), gradW.data_ptr<float>(),
       gradV.data_ptr<float>(), (unsigned long long*)touched.data_ptr(),
       nfields, (int)sorted_fids.numel(), K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 std::vector<at::Tensor> ffm_block_emit(at::Tensor row_of_entry,
@@ -537,8 +566,10 @@ std::vector<at::Tensor> ffm_block_emit(at::Tensor row_of_entry,
                                        at::Tensor V, at::Tensor dpred) {
   check_cuda_i32(row_of_entry, "row_of_entry");
   check_cuda_f32(V, "V");
+  check_ffm_v(V);
   const int nfields = (int)V.size(1);
   const int K = (int)V.size(2);
+  check_ffm_block_lds(nfields, K, "ffm_block_emit");
   const auto nnz = fids.numel();
   auto gblocks = at::empty({nnz, (long)nfields * K}, V.options());
   auto gw = at::empty({nnz}, V.options());
@@ -548,6 +579,7 @@ std::vector<at::Tensor> ffm_block_emit(at::Tensor row_of_entry,
       V.data_ptr<float>(), dpred.data_ptr<float>(),
       gblocks.data_ptr<float>(), gw.data_ptr<float>(), nfields, (int)nnz, K,
       cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return {gw, gblocks};
 }
 
@@ -557,12 +589,17 @@ void ffm_blocks_apply(at::Tensor sorted_fids, at::Tensor perm,
   check_cuda_i32(sorted_fids, "sorted_fids");
   auto perm_i = perm32(perm).contiguous();
   const int D = (int)gblocks.size(1);
+  const long need = lightctr::ffm_blocks_apply_lds_bytes(D);
+  const long have = lightctr::ffm_max_lds_per_block();
+  CHK(need <= have, "ffm_blocks_apply: D=", D, " needs ", need,
+      " bytes of LDS per block, the device gives ", have);
   lightctr::ffm_blocks_apply_launch(
       sorted_fids.data_ptr<int>(), perm_i.data_ptr<int>(),
       gblocks.data_ptr<float>(), gw.data_ptr<float>(),
       gradW.data_ptr<float>(), gradV.data_ptr<float>(),
       (unsigned long long*)touched.data_ptr(), D,
       (int)sorted_fids.numel(), cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 at::Tensor row_index(at::Tensor row_ptr, int64_t nnz) {
@@ -1346,6 +1383,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ffm_sorted_backward", &ffm_sorted_backward,
         "FFM sorted segment-reduce backward (LDS block accumulate)");
   m.def("row_index", &row_index, "entry -> row index from row_ptr");
+  m.def("ffm_block_lds_bytes", &lightctr::ffm_block_lds_bytes,
+        "dynamic LDS per block of ffm_sorted_backward / ffm_block_emit",
+        py::arg("nfields"), py::arg("K"));
+  m.def("ffm_max_lds_per_block", &lightctr::ffm_max_lds_per_block,
+        "per-block LDS limit of the current device, in bytes");
   m.def("ffm_block_emit", &ffm_block_emit,
         "FFM per-entry [nf,K] gradient blocks (wave/entry)");
   m.def("ffm_blocks_apply", &ffm_blocks_apply,

@@ -908,6 +908,32 @@ bool ffm_staged_eligible(int nfields, int K, int maxn) {
   return ffm_row_emit_lds_bytes(nfields, K, maxn, 8) <= (64 << 10);
 }
 
+// ffm_sorted_backward / ffm_block_emit: one [nfields, K+1] fp32 block per
+// wave, 4 waves per block. A request past the device's per-block LDS limit
+// is a launch error, which would leave the gradients unwritten; the
+// bindings compare it with ffm_max_lds_per_block() up front.
+static constexpr int kFfmBlockWpb = 4;
+
+long ffm_block_lds_bytes(int nfields, int K) {
+  return (long)kFfmBlockWpb * nfields * (K + 1) * (long)sizeof(float);
+}
+
+// dynamic LDS of ffm_blocks_apply: one [D] fp32 accumulator per wave
+static constexpr int kFfmApplyWpb = 4;
+
+long ffm_blocks_apply_lds_bytes(int D) {
+  return (long)kFfmApplyWpb * D * (long)sizeof(float);
+}
+
+// what one block of the current device can get (160 KB on gfx950)
+long ffm_max_lds_per_block() {
+  int dev = 0, v = 0;
+  LCTR_CHECK_HIP(hipGetDevice(&dev));
+  LCTR_CHECK_HIP(hipDeviceGetAttribute(
+      &v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+  return v;
+}
+
 void ffm_fwd_staged_launch(const int* row_ptr, const int* fields,
                            const int* fids, const float* vals, const float* W,
                            const float* V, float* pred, int nfields, int B,
@@ -1056,7 +1082,8 @@ void ffm_block_emit_launch(const int* row_of_entry, const int* row_ptr,
   const int wpb = 4;
   dim3 block(wpb * LCTR_WAVE);
   dim3 grid((nnz + wpb - 1) / wpb);
-  const size_t lds = (size_t)wpb * nfields * (K + 1) * sizeof(float);
+  static_assert(wpb == kFfmBlockWpb, "ffm_block_lds_bytes assumes wpb");
+  const size_t lds = (size_t)ffm_block_lds_bytes(nfields, K);
   DISPATCH_FFM_K(K, hipLaunchKernelGGL((ffm_block_emit_kernel<KC>), grid,
                                        block, lds, stream, row_of_entry,
                                        row_ptr, fields, fids, vals, V, dpred,
@@ -1074,7 +1101,8 @@ void ffm_blocks_apply_launch(const int* sorted_fids, const int* perm,
   const int nwaves = (nnz + chunk - 1) / chunk;
   dim3 block(wpb * LCTR_WAVE);
   dim3 grid((nwaves + wpb - 1) / wpb);
-  const size_t lds = (size_t)wpb * D * sizeof(float);
+  static_assert(wpb == kFfmApplyWpb, "ffm_blocks_apply_lds_bytes assumes wpb");
+  const size_t lds = (size_t)ffm_blocks_apply_lds_bytes(D);
   hipLaunchKernelGGL(ffm_blocks_apply_kernel, grid, block, lds, stream,
                      sorted_fids, perm, gblocks, gw, gradW, gradV, touched,
                      D, nnz, chunk);
@@ -1105,7 +1133,8 @@ void ffm_sorted_backward_launch(const int* sorted_fids, const int* perm,
   const int nwaves = (nnz + chunk - 1) / chunk;
   dim3 block(wpb * LCTR_WAVE);
   dim3 grid((nwaves + wpb - 1) / wpb);
-  const size_t lds = (size_t)wpb * nfields * (K + 1) * sizeof(float);
+  static_assert(wpb == kFfmBlockWpb, "ffm_block_lds_bytes assumes wpb");
+  const size_t lds = (size_t)ffm_block_lds_bytes(nfields, K);
   DISPATCH_FFM_K(K, hipLaunchKernelGGL((ffm_sorted_backward_kernel<KC>),
                                        grid, block, lds, stream, sorted_fids,
                                        perm, row_of_entry, row_ptr, fields,

@@ -90,6 +90,11 @@ void ffm_forward_pp_launch(const int* row_ptr, const int* fields,
                            float* pred, int nfields, int B, int K,
                            ihipStream_t* stream);
 bool ffm_staged_eligible(int nfields, int K, int maxn);
+// dynamic LDS of ffm_sorted_backward / ffm_block_emit and of
+// ffm_blocks_apply, and the per-block LDS limit of the current device
+long ffm_block_lds_bytes(int nfields, int K);
+long ffm_blocks_apply_lds_bytes(int D);
+long ffm_max_lds_per_block();
 void ffm_fwd_staged_launch(const int* row_ptr, const int* fields,
                            const int* fids, const float* vals, const float* W,
                            const float* V, float* pred, int nfields, int B,

@@ -476,6 +476,12 @@ def test_ffm_large_field_product_falls_back():
     vals = torch.ones(B * nf).cuda()
     row_ptr = (torch.arange(B + 1, dtype=torch.int32) * nf).cuda()
     labels = (torch.rand(B, generator=g) > 0.5).float().cuda()
+    W0, V0 = m.W.clone(), m.V.clone()
     for _ in range(3):
         loss = m.train_step(row_ptr, fields, fids, vals, labels)
         assert torch.isfinite(loss).all()
+    # a rejected launch would leave the gradients zero and the step a no-op
+    live = torch.unique(fids).long()
+    assert (m.W[live] != W0[live]).all()
+    assert (m.V[live] != V0[live]).any(dim=(1, 2)).all()
+    assert torch.isfinite(m.V).all()
