@@ -10,6 +10,8 @@ command:
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
     python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
         --data dense.csv ...      (dense rows; served by the compiled forest)
+    python -m lightctr_amd.cli neighbors --load emb.pt --words a0,b1 \
+        --topk 5 [--index pq --pq-sub 4 --rerank 32]
 
 Distributed modes are launched via torch.distributed.run (one rank per
 GPU), selecting --mode ring|sharded|ps at runtime.
@@ -424,9 +426,49 @@ def cmd_predict(args) -> int:
     return 0
 
 
+def cmd_neighbors(args) -> int:
+    """Nearest words of a saved embedding, all query words in one batched
+    search (predict/knn.py)."""
+    from .models.embedding import EmbedHyper, EmbedModel
+
+    dev = _device(args)
+    if not args.load:
+        print("neighbors needs --load", file=sys.stderr)
+        return 2
+    dim = torch.load(args.load, map_location="cpu",
+                     weights_only=False)["E"].shape[1]
+    m = EmbedModel.load_pretrain(args.load, EmbedHyper(dim=dim), device=dev)
+    words = [w for w in args.words.split(",") if w]
+    missing = [w for w in words if w not in m.word2id]
+    if missing or not words:
+        print(f"words not in the vocabulary: {missing}", file=sys.stderr)
+        return 2
+    kw, skw = {}, {}
+    if args.index == "pq":
+        kw = {"n_sub": args.pq_sub, "seed": args.seed}
+        if args.rerank:
+            skw = {"rerank": args.rerank}
+    m.build_index(kind=args.index, **kw)  # cosine ranking
+    res = m.neighbors(words, args.topk, **skw)
+    print(json.dumps({"index": args.index,
+                      "neighbors": {w: [[n, round(s, 6)] for n, s in r]
+                                    for w, r in zip(words, res)}}))
+    return 0
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="lightctr_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
+    p = sub.add_parser("neighbors")
+    p.set_defaults(fn=cmd_neighbors)
+    p.add_argument("--load", default=None, help="file of train --model embed")
+    p.add_argument("--words", required=True, help="comma-separated words")
+    p.add_argument("--topk", type=int, default=5)
+    p.add_argument("--index", default="flat", choices=("flat", "pq"))
+    p.add_argument("--pq-sub", type=int, default=4)
+    p.add_argument("--rerank", type=int, default=0)
+    p.add_argument("--device", default=None)
+    p.add_argument("--seed", type=int, default=0)
     for name, fn in (("train", cmd_train), ("predict", cmd_predict)):
         p = sub.add_parser(name)
         p.set_defaults(fn=fn)

@@ -215,6 +215,45 @@ class EmbedModel:
         return [(self.vocab[i], float(v)) for v, i in zip(vals, idx)
                 if i != wid][:k]
 
+    def build_index(self, kind: str = "flat", metric: str = "ip", **kw):
+        """Index the table for batched search (predict/knn.py): ``flat``
+        is exact, ``pq`` takes PQIndex.build's keywords (n_sub, ...). For
+        ``ip`` a unit-length copy of E is indexed, so the ranking is the
+        cosine ranking of ``most_similar``. Rebuild after more training."""
+        from ..predict.knn import FlatIndex, PQIndex
+
+        E = self.E
+        if metric == "ip":
+            E = E / E.norm(dim=1, keepdim=True).clamp(min=1e-12)
+        E = E.contiguous()
+        if kind == "flat":
+            index = FlatIndex(E, metric)
+        elif kind == "pq":
+            kw.setdefault("n_sub", 4)
+            index = PQIndex.build(E, metric=metric, **kw)
+        else:
+            raise ValueError(f"kind must be 'flat' or 'pq', got {kind!r}")
+        self._index, self._index_vectors = index, E
+        return index
+
+    def neighbors(self, words: list[str], k: int = 5, **search_kw):
+        """Per word, its k nearest other words as [(word, score)] from the
+        index of ``build_index`` (built with the defaults if absent), all
+        words in one batched search. score is the cosine similarity for
+        an ``ip`` index and the squared distance for ``l2``."""
+        index = getattr(self, "_index", None) or self.build_index()
+        wids = [self.word2id[w] for w in words]
+        Q = self._index_vectors[torch.tensor(wids, dtype=torch.long,
+                                             device=self.device)]
+        ids, dist = index.search(Q, k + 1, **search_kw)
+        sign = -1.0 if index.metric == "ip" else 1.0
+        out = []
+        for wid, row_i, row_d in zip(wids, ids.tolist(), dist.tolist()):
+            hits = [(self.vocab[i], sign * d)
+                    for i, d in zip(row_i, row_d) if i >= 0 and i != wid]
+            out.append(hits[:k])
+        return out
+
     def save(self, path: str):
         torch.save({"vocab": self.vocab, "E": self.E,
                     "counts": self.counts}, path)

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 #include <vector>
 
@@ -1306,6 +1307,148 @@ at::Tensor gbm_forest(at::Tensor X, at::Tensor nodes, at::Tensor tree_off,
   return out;
 }
 
+// ---- nearest-neighbour search (predict/knn.py) ----
+
+void check_knn_k(int64_t k) {
+  CHK(k >= 1 && k <= lightctr::knn_max_k(), "k must be in [1, ",
+      lightctr::knn_max_k(), "], got ", k);
+}
+
+void check_knn_metric(int64_t metric) {
+  CHK(metric == 0 || metric == 1, "metric must be 0 (l2) or 1 (ip)");
+}
+
+// (ids, dist) preset to the empty result, for N == 0
+std::vector<at::Tensor> knn_outputs(int64_t nq, int64_t k,
+                                    const at::Tensor& like, bool fill) {
+  auto ids = at::empty({nq, k}, like.options().dtype(at::kInt));
+  auto dist = at::empty({nq, k}, like.options().dtype(at::kFloat));
+  if (fill) {
+    ids.fill_(-1);
+    dist.fill_(std::numeric_limits<float>::infinity());
+  }
+  return {ids, dist};
+}
+
+at::Tensor pq_lut(at::Tensor Q, at::Tensor centroids, int64_t metric) {
+  check_cuda_f32(Q, "Q");
+  check_cuda_f32(centroids, "centroids");
+  check_knn_metric(metric);
+  CHK(Q.dim() == 2, "Q must be [nq, dim]");
+  CHK(centroids.dim() == 3, "centroids must be [n_sub, ncb, d_sub]");
+  const int64_t nq = Q.size(0), n_sub = centroids.size(0),
+                ncb = centroids.size(1), d_sub = centroids.size(2);
+  CHK(n_sub >= 1 && n_sub <= lightctr::knn_max_sub(), "n_sub must be in [1, ",
+      lightctr::knn_max_sub(), "], got ", n_sub);
+  CHK(ncb >= 1 && ncb <= 256, "ncb must be in [1, 256], got ", ncb);
+  CHK(d_sub >= 1 && n_sub * d_sub == Q.size(1), "Q has ", Q.size(1),
+      " columns, the centroids span ", n_sub * d_sub);
+  CHK(nq * n_sub * ncb < ((int64_t)1 << 31) * 256, "LUT too large");
+  auto lut = at::empty({nq, n_sub, ncb}, Q.options());
+  if (nq == 0) return lut;
+  lightctr::pq_lut_launch(Q.data_ptr<float>(), centroids.data_ptr<float>(),
+                          lut.data_ptr<float>(), (long)nq, (int)n_sub,
+                          (int)ncb, (int)d_sub, (int)metric, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return lut;
+}
+
+std::vector<at::Tensor> pq_adc_topk(at::Tensor lut, at::Tensor codes,
+                                    int64_t ncb, int64_t k) {
+  check_cuda_f32(lut, "lut");
+  CHK(codes.is_cuda(), "codes must be on GPU");
+  CHK(codes.scalar_type() == at::kByte, "codes must be uint8");
+  CHK(lut.dim() == 3, "lut must be [nq, n_sub, ncb]");
+  CHK(codes.dim() == 2, "codes must be [N, n_sub]");
+  check_knn_k(k);
+  const int64_t nq = lut.size(0), n_sub = lut.size(1), N = codes.size(0);
+  CHK(n_sub >= 1 && n_sub <= lightctr::knn_max_sub(), "n_sub must be in [1, ",
+      lightctr::knn_max_sub(), "], got ", n_sub);
+  CHK(ncb >= 1 && ncb <= 256, "ncb must be in [1, 256], got ", ncb);
+  CHK(lut.size(2) == ncb, "lut is ", lut.size(2), " wide, ncb is ", ncb);
+  CHK(codes.size(1) == n_sub, "codes have ", codes.size(1),
+      " columns, lut has ", n_sub, " sub-vectors");
+  CHK(N < ((int64_t)1 << 31), "N must be below 2^31");
+  CHK(N <= 1 || n_sub == 1 || codes.stride(1) == 1,
+      "codes rows must be dense (column stride 1)");
+  CHK(N <= 1 || codes.stride(0) >= n_sub, "codes rows overlap");
+  const long need = lightctr::pq_adc_lds_bytes((int)n_sub, (int)ncb);
+  const long have = lightctr::ffm_max_lds_per_block();
+  CHK(need <= have, "pq_adc_topk: n_sub=", n_sub, ", ncb=", ncb, " needs ",
+      need, " bytes of LDS per block, the device gives ", have);
+  auto out = knn_outputs(nq, k, lut, N == 0);
+  if (nq == 0 || N == 0) return out;
+  const long rows = lightctr::knn_slice_rows((long)N, (long)nq);
+  const int64_t n_slices = (N + rows - 1) / rows;
+  CHK(nq * n_slices < ((int64_t)1 << 31), "too many blocks");
+  at::Tensor partial;
+  if (n_slices > 1)
+    partial = at::empty({nq, n_slices, k}, lut.options().dtype(at::kLong));
+  lightctr::pq_adc_topk_launch(
+      lut.data_ptr<float>(), codes.data_ptr<unsigned char>(),
+      (long)(N > 1 ? codes.stride(0) : n_sub), (long)N, (long)nq, (int)n_sub,
+      (int)ncb, (int)k, rows, (int)n_slices,
+      n_slices > 1 ? partial.data_ptr() : nullptr, out[0].data_ptr<int>(),
+      out[1].data_ptr<float>(), cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  if (n_slices > 1) {
+    lightctr::knn_merge_launch(partial.data_ptr(), (long)nq, (int)n_slices,
+                               (int)k, 0, out[0].data_ptr<int>(),
+                               out[1].data_ptr<float>(), cur_stream());
+    C10_CUDA_KERNEL_LAUNCH_CHECK();
+  }
+  return out;
+}
+
+std::vector<at::Tensor> flat_topk(at::Tensor X, at::Tensor Q, int64_t metric,
+                                  int64_t k, c10::optional<at::Tensor> cand) {
+  check_cuda_f32(Q, "Q");
+  CHK(X.is_cuda(), "X must be on GPU");
+  CHK(X.scalar_type() == at::kFloat, "X must be fp32");
+  CHK(X.dim() == 2 && Q.dim() == 2, "X must be [N, dim], Q [nq, dim]");
+  check_knn_metric(metric);
+  check_knn_k(k);
+  const int64_t N = X.size(0), dim = X.size(1), nq = Q.size(0);
+  CHK(dim >= 1 && dim <= lightctr::knn_max_dim(), "dim must be in [1, ",
+      lightctr::knn_max_dim(), "], got ", dim);
+  CHK(Q.size(1) == dim, "Q has ", Q.size(1), " columns, X has ", dim);
+  CHK(N < ((int64_t)1 << 31), "N must be below 2^31");
+  CHK(N <= 1 || dim == 1 || X.stride(1) == 1,
+      "X rows must be dense (column stride 1)");
+  CHK(N <= 1 || X.stride(0) >= dim, "X rows overlap");
+  int64_t n_items = N;
+  const int* cand_p = nullptr;
+  if (cand.has_value()) {
+    check_cuda_i32(*cand, "cand");
+    CHK(cand->dim() == 2 && cand->size(0) == nq, "cand must be [nq, R]");
+    n_items = cand->size(1);
+    cand_p = cand->data_ptr<int>();
+  }
+  auto out = knn_outputs(nq, k, Q, N == 0 || n_items == 0);
+  if (nq == 0 || N == 0 || n_items == 0) return out;
+  const long rows = lightctr::knn_slice_rows((long)n_items, (long)nq);
+  const int64_t n_slices = (n_items + rows - 1) / rows;
+  CHK(nq * n_slices < ((int64_t)1 << 31), "too many blocks");
+  at::Tensor partial;
+  if (n_slices > 1)
+    partial = at::empty({nq, n_slices, k}, Q.options().dtype(at::kLong));
+  lightctr::flat_topk_launch(
+      X.data_ptr<float>(), (long)(N > 1 ? X.stride(0) : dim), (long)N,
+      (int)dim, Q.data_ptr<float>(), (long)nq, cand_p, (long)n_items,
+      (int)metric, (int)k, rows, (int)n_slices,
+      n_slices > 1 ? partial.data_ptr() : nullptr, out[0].data_ptr<int>(),
+      out[1].data_ptr<float>(), cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  if (n_slices > 1) {
+    lightctr::knn_merge_launch(partial.data_ptr(), (long)nq, (int)n_slices,
+                               (int)k, cand_p ? 1 : 0,
+                               out[0].data_ptr<int>(),
+                               out[1].data_ptr<float>(), cur_stream());
+    C10_CUDA_KERNEL_LAUNCH_CHECK();
+  }
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1488,4 +1631,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("beta"), py::arg("l1"), py::arg("l2"),
         py::arg("v_adagrad") = 0, py::arg("v_lr") = 0.05,
         py::arg("v_eps") = 1e-8, py::arg("v_l2") = 1e-5);
+  m.def("pq_lut", &pq_lut,
+        "PQ distance tables [nq, n_sub, ncb]; metric 0 = l2, 1 = ip",
+        py::arg("Q"), py::arg("centroids"), py::arg("metric"));
+  m.def("pq_adc_topk", &pq_adc_topk,
+        "ADC scan of uint8 codes + top-k -> (ids int32, dist fp32) [nq, k]",
+        py::arg("lut"), py::arg("codes"), py::arg("ncb"), py::arg("k"));
+  m.def("flat_topk", &flat_topk,
+        "exact scan (or per-query candidate list) + top-k -> (ids, dist)",
+        py::arg("X"), py::arg("Q"), py::arg("metric"), py::arg("k"),
+        py::arg("cand") = py::none());
+  m.def("knn_max_k", &lightctr::knn_max_k, "largest k of the top-k kernels");
+  m.def("knn_max_sub", &lightctr::knn_max_sub,
+        "largest n_sub of pq_adc_topk");
+  m.def("knn_max_dim", &lightctr::knn_max_dim, "largest dim of flat_topk");
+  m.def("knn_slice_rows", &lightctr::knn_slice_rows,
+        "rows per block slice for n rows and nq queries", py::arg("n"),
+        py::arg("nq"));
 }

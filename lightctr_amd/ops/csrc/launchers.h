@@ -295,4 +295,29 @@ void gbm_forest_launch(const float* X, const void* nodes, const int* tree_off,
                        int D, int T, int K, int max_depth, int fid_offset,
                        int mode, ihipStream_t* stream);
 
+// --- knn_kernels.hip ---
+// top-k search (predict/knn.py): ids int32 / dist fp32 [nq, k] in ascending
+// (dist, id) order, (-1, +inf) past the row count. `partial` is the
+// [nq, n_slices, k] 8-byte key buffer of the slices, merged by
+// knn_merge_launch when n_slices > 1 (dedup: equal keys count once).
+int knn_max_k();
+int knn_max_sub();
+int knn_max_dim();
+long knn_slice_rows(long n, long nq);
+long pq_adc_lds_bytes(int n_sub, int ncb);
+void pq_lut_launch(const float* Q, const float* C, float* lut, long nq,
+                   int n_sub, int ncb, int d_sub, int ip,
+                   ihipStream_t* stream);
+void pq_adc_topk_launch(const float* lut, const unsigned char* codes,
+                        long stride, long N, long nq, int n_sub, int ncb,
+                        int k, long slice_rows, int n_slices, void* partial,
+                        int* ids, float* dist, ihipStream_t* stream);
+void flat_topk_launch(const float* X, long stride, long N, int dim,
+                      const float* Q, long nq, const int* cand, long n_items,
+                      int ip, int k, long slice_rows, int n_slices,
+                      void* partial, int* ids, float* dist,
+                      ihipStream_t* stream);
+void knn_merge_launch(const void* partial, long nq, int n_slices, int k,
+                      int dedup, int* ids, float* dist, ihipStream_t* stream);
+
 }  // namespace lightctr
