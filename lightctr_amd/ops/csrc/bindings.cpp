@@ -4,11 +4,13 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <c10/cuda/CUDAException.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "launchers.h"
@@ -761,8 +763,17 @@ at::Tensor gemm_wgrad_bf16(at::Tensor At, at::Tensor Bt, int64_t M,
           At.is_contiguous(), "At must be cuda bf16 [K,M]");
   CHK(Bt.is_cuda() && Bt.scalar_type() == at::kBFloat16 &&
           Bt.is_contiguous(), "Bt must be cuda bf16 [K,N]");
+  const int64_t imax = std::numeric_limits<int>::max();
+  CHK(M >= 1 && N >= 1 && K >= 1 && M <= imax && N <= imax && K <= imax,
+      "gemm_wgrad: M, N, K must be in [1, 2^31)");
+  CHK(At.numel() == K * M, "At must hold K*M = ", K * M, " elements, has ",
+      At.numel());
+  CHK(Bt.numel() == K * N, "Bt must hold K*N = ", K * N, " elements, has ",
+      Bt.numel());
   CHK(lightctr::gemm_wgrad_eligible((int)M, (int)N, (int)K, 1, 1),
       "shape not eligible for the wgrad kernel");
+  CHK((((uintptr_t)At.data_ptr() | (uintptr_t)Bt.data_ptr()) & 15) == 0,
+      "the wgrad kernel needs 16-byte-aligned operand base addresses");
   auto C = at::empty({M, N}, At.options().dtype(at::kFloat));
   lightctr::gemm_wgrad_bf16_launch(At.data_ptr(), Bt.data_ptr(),
                                    C.data_ptr<float>(), (int)M, (int)N,
@@ -882,12 +893,148 @@ void fm_ftrl_apply(at::Tensor uniq, at::Tensor count, at::Tensor W,
 
 // ---- dense NN ops ----
 
-at::Tensor gemm_bf16(at::Tensor A, at::Tensor Bst,
-                     c10::optional<at::Tensor> bias, int64_t M, int64_t N,
-                     int64_t K, int64_t transA, int64_t transB, int64_t act,
-                     bool emit_bf16) {
+// The GEMM kernels index their operands from M, N, K alone; everything
+// they assume about the tensors is checked here, as exceptions. Returns
+// the bias pointer (nullptr without bias).
+const float* check_gemm_args(const at::Tensor& A, const at::Tensor& Bst,
+                             const c10::optional<at::Tensor>& bias,
+                             int64_t M, int64_t N, int64_t K,
+                             int64_t transA, int64_t transB, int64_t act) {
+  const int64_t imax = std::numeric_limits<int>::max();
+  CHK(M >= 1 && N >= 1 && K >= 1, "gemm: M, N, K must be >= 1, got ", M,
+      ", ", N, ", ", K);
+  CHK(M <= imax && N <= imax && K <= imax, "gemm: M, N, K must fit int32");
+  CHK(transA == 0 || transA == 1, "gemm: transA must be 0 or 1, got ",
+      transA);
+  CHK(transB == 0 || transB == 1, "gemm: transB must be 0 or 1, got ",
+      transB);
+  CHK(act >= 0 && act <= 2, "gemm: act must be 0, 1 or 2, got ", act);
   CHK(A.is_cuda() && A.scalar_type() == at::kBFloat16, "A must be bf16 GPU");
-  CHK(Bst.is_cuda() && Bst.scalar_type() == at::kBFloat16, "Bst bf16");
+  CHK(Bst.is_cuda() && Bst.scalar_type() == at::kBFloat16,
+      "Bst must be bf16 GPU");
+  CHK(A.is_contiguous(), "A must be contiguous");
+  CHK(Bst.is_contiguous(), "Bst must be contiguous");
+  CHK(A.numel() == M * K, "A must hold M*K = ", M * K, " elements, has ",
+      A.numel());
+  CHK(Bst.numel() == N * K, "Bst must hold N*K = ", N * K,
+      " elements, has ", Bst.numel());
+  if (!bias.has_value()) return nullptr;
+  check_cuda_f32(*bias, "bias");
+  CHK(bias->numel() == N, "bias must hold N = ", N, " elements, has ",
+      bias->numel());
+  return bias->data_ptr<float>();
+}
+
+bool gemm_aligned16(const at::Tensor& A, const at::Tensor& Bst) {
+  return (((uintptr_t)A.data_ptr() | (uintptr_t)Bst.data_ptr()) & 15) == 0;
+}
+
+std::string gemm_route_name(const lightctr::GemmRoute& r) {
+  switch (r.body) {
+    case lightctr::GEMM_BODY_GENERIC:
+      return "generic:split=" + std::to_string(r.split_z);
+    case lightctr::GEMM_BODY_256:
+      return "gemm256_p" + std::to_string(r.pipe) + "_b" +
+             std::to_string((int)r.burst);
+    case lightctr::GEMM_BODY_P8:
+      return std::string(r.lite ? "p8_lite" : "p8_full") +
+             (r.xcd ? "_xcd" : "") + (r.apipe ? "_apipe" : "");
+    case lightctr::GEMM_BODY_V2: return "v2";
+    case lightctr::GEMM_BODY_N128: return "n128";
+    case lightctr::GEMM_BODY_WGRAD128:
+      return "wgrad128:split=" + std::to_string(r.split_z);
+    case lightctr::GEMM_BODY_GEMV_N1: return "gemv_n1";
+    case lightctr::GEMM_BODY_WROWSUM_M1: return "wrowsum_m1";
+    case lightctr::GEMM_BODY_SMALL_WGRAD: return "small_wgrad";
+    case lightctr::GEMM_BODY_OUTER_K1: return "outer_k1";
+  }
+  return "unknown";
+}
+
+// Name of the body the default dispatch picks in this process for
+// 16 B-aligned operands; "generic" and "wgrad128" carry the split-K
+// fan-out they would request (":split=0" = none).
+std::string gemm_bf16_route(int64_t M, int64_t N, int64_t K, int64_t transA,
+                            int64_t transB, bool has_bias, int64_t act,
+                            bool emit_bf16) {
+  const int64_t imax = std::numeric_limits<int>::max();
+  CHK(M >= 1 && N >= 1 && K >= 1 && M <= imax && N <= imax && K <= imax,
+      "gemm: M, N, K must be in [1, 2^31)");
+  CHK((transA == 0 || transA == 1) && (transB == 0 || transB == 1),
+      "gemm: transA, transB must be 0 or 1");
+  CHK(act >= 0 && act <= 2, "gemm: act must be 0, 1 or 2, got ", act);
+  return gemm_route_name(lightctr::gemm_bf16_pick(
+      (int)M, (int)N, (int)K, (int)transA, (int)transB, has_bias, (int)act,
+      emit_bf16, true));
+}
+
+// Launch one named GEMM body directly, whatever the default dispatch or
+// the environment would pick. Raises unless the body accepts the shape,
+// layout, epilogue and operand alignment.
+std::vector<at::Tensor> gemm_bf16_variant(
+    at::Tensor A, at::Tensor Bst, c10::optional<at::Tensor> bias, int64_t M,
+    int64_t N, int64_t K, int64_t transA, int64_t transB, int64_t act,
+    bool emit_bf16, std::string variant, int64_t split_z) {
+  const float* bias_ptr =
+      check_gemm_args(A, Bst, bias, M, N, K, transA, transB, act);
+  const int m = (int)M, n = (int)N, k = (int)K, ta = (int)transA,
+            tb = (int)transB;
+  const bool plain = bias_ptr == nullptr && act == 0 && !emit_bf16;
+  const bool aligned = gemm_aligned16(A, Bst);
+  CHK(split_z >= 0 && split_z <= 1024, "split_z must be in [0, 1024], got ",
+      split_z);
+  lightctr::GemmRoute r;
+  r.split_z = (int)split_z;
+  bool splits = false;  // body has a split-K form
+  bool ok = false;      // body accepts shape and layout
+  bool glds = true;     // body needs 16 B-aligned operand bases
+  if (variant == "generic") {
+    r.body = lightctr::GEMM_BODY_GENERIC;
+    splits = ok = true;
+    glds = false;
+  } else if (variant.rfind("gemm256_p", 0) == 0 && variant.size() == 13 &&
+             variant.compare(10, 2, "_b") == 0) {
+    r.body = lightctr::GEMM_BODY_256;
+    r.pipe = variant[9] - '0';
+    const int burst = variant[12] - '0';
+    CHK(r.pipe >= 0 && r.pipe <= 2 && (burst == 0 || burst == 1),
+        "unknown GEMM variant '", variant, "'");
+    r.burst = burst == 1;
+    ok = lightctr::gemm256_eligible(m, n, k, ta, tb);
+    CHK(!(r.pipe == 2 && K % 64 != 0),
+        "gemm256 pipe 2 takes K % 64 == 0 only, got K = ", K);
+  } else if (variant == "p8_lite" || variant == "p8_lite_xcd" ||
+             variant == "p8_full" || variant == "p8_full_xcd" ||
+             variant == "p8_lite_apipe") {
+    r.body = lightctr::GEMM_BODY_P8;
+    r.lite = variant.compare(3, 4, "lite") == 0;
+    r.xcd = variant.find("_xcd") != std::string::npos;
+    r.apipe = variant.find("_apipe") != std::string::npos;
+    ok = lightctr::gemm256p8_eligible(m, n, k, ta, tb);
+  } else if (variant == "v2") {
+    r.body = lightctr::GEMM_BODY_V2;
+    ok = lightctr::gemm256v2_eligible(m, n, k, ta, tb);
+  } else if (variant == "n128") {
+    // the kernel itself takes any N and any K that is a whole number of
+    // tiles; the default dispatch narrows that further
+    r.body = lightctr::GEMM_BODY_N128;
+    ok = ta == 0 && tb == 0 && M % 256 == 0 && K % 64 == 0;
+  } else if (variant == "wgrad128") {
+    r.body = lightctr::GEMM_BODY_WGRAD128;
+    splits = true;
+    ok = lightctr::gemm_wgrad_eligible(m, n, k, ta, tb);
+    CHK(plain, "wgrad128 has no bias / activation / bf16 epilogue");
+  } else {
+    CHK(false, "unknown GEMM variant '", variant, "'");
+  }
+  CHK(ok, "GEMM variant '", variant, "' does not accept M=", M, " N=", N,
+      " K=", K, " transA=", transA, " transB=", transB);
+  CHK(!glds || aligned, "GEMM variant '", variant,
+      "' needs 16-byte-aligned operand base addresses");
+  CHK(splits || split_z == 0, "GEMM variant '", variant,
+      "' has no split-K form");
+  CHK(split_z == 0 || plain,
+      "split-K has no bias / activation / bf16 epilogue");
   auto C = at::empty({M, N}, A.options().dtype(at::kFloat));
   at::Tensor Cbf;
   void* cbf_ptr = nullptr;
@@ -895,8 +1042,26 @@ at::Tensor gemm_bf16(at::Tensor A, at::Tensor Bst,
     Cbf = at::empty({M, N}, A.options());
     cbf_ptr = Cbf.data_ptr();
   }
+  lightctr::gemm_bf16_run(r, A.data_ptr(), Bst.data_ptr(), bias_ptr,
+                          C.data_ptr<float>(), cbf_ptr, m, n, k, ta, tb,
+                          (int)act, cur_stream());
+  if (emit_bf16) return {C, Cbf};
+  return {C};
+}
+
+at::Tensor gemm_bf16(at::Tensor A, at::Tensor Bst,
+                     c10::optional<at::Tensor> bias, int64_t M, int64_t N,
+                     int64_t K, int64_t transA, int64_t transB, int64_t act,
+                     bool emit_bf16) {
   const float* bias_ptr =
-      bias.has_value() ? bias->data_ptr<float>() : nullptr;
+      check_gemm_args(A, Bst, bias, M, N, K, transA, transB, act);
+  auto C = at::empty({M, N}, A.options().dtype(at::kFloat));
+  at::Tensor Cbf;
+  void* cbf_ptr = nullptr;
+  if (emit_bf16) {
+    Cbf = at::empty({M, N}, A.options());
+    cbf_ptr = Cbf.data_ptr();
+  }
   lightctr::gemm_bf16_launch(A.data_ptr(), Bst.data_ptr(), bias_ptr,
                              C.data_ptr<float>(), cbf_ptr, (int)M, (int)N,
                              (int)K, (int)transA, (int)transB, (int)act,
@@ -909,12 +1074,10 @@ std::vector<at::Tensor> gemm_bf16_full(at::Tensor A, at::Tensor Bst,
                                        int64_t M, int64_t N, int64_t K,
                                        int64_t transA, int64_t transB,
                                        int64_t act) {
-  CHK(A.is_cuda() && A.scalar_type() == at::kBFloat16, "A must be bf16 GPU");
-  CHK(Bst.is_cuda() && Bst.scalar_type() == at::kBFloat16, "Bst bf16");
+  const float* bias_ptr =
+      check_gemm_args(A, Bst, bias, M, N, K, transA, transB, act);
   auto C = at::empty({M, N}, A.options().dtype(at::kFloat));
   auto Cbf = at::empty({M, N}, A.options());
-  const float* bias_ptr =
-      bias.has_value() ? bias->data_ptr<float>() : nullptr;
   lightctr::gemm_bf16_launch(A.data_ptr(), Bst.data_ptr(), bias_ptr,
                              C.data_ptr<float>(), Cbf.data_ptr(), (int)M,
                              (int)N, (int)K, (int)transA, (int)transB,
@@ -1613,6 +1776,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NFM per-entry grads for sorted apply");
   m.def("bitmap_compact", &bitmap_compact, "touched bitmap -> fid list");
   m.def("wg_probe", &wg_probe, "wgrad staging/tr-read debug probe");
+  m.def("gemm_bf16_variant", &gemm_bf16_variant,
+        "launch one named GEMM body directly; returns [C] or [C, Cbf]");
+  m.def("gemm_bf16_route", &gemm_bf16_route,
+        "name of the GEMM body the default dispatch picks");
   m.def("gemm_wgrad_bf16", &gemm_wgrad_bf16,
         "K-major x K-major wgrad GEMM (tr16 fragment reads)");
   m.def("im2col_bf16", &im2col_bf16,

@@ -301,11 +301,9 @@ bool gemm256_eligible(int M, int N, int K, int transA, int transB) {
          K % 8 == 0 && K >= 32;
 }
 
-void gemm256_bf16_launch(const void* A, const void* Bst, const float* bias,
-                         float* C, void* Cbf, int M, int N, int K, int act,
-                         hipStream_t stream) {
-  dim3 block(512);
-  dim3 grid(N / 256, M / 256);
+// The environment's choice of body for depth K (the tail flag itself is
+// derived from K in the launcher).
+void gemm256_default_cfg(int K, bool* burst_out, int* pipe_out) {
   static const bool burst = [] {
     const char* e = getenv("LCTR_GEMM_BURST");
     return e && e[0] == '1';
@@ -319,6 +317,21 @@ void gemm256_bf16_launch(const void* A, const void* Bst, const float* bias,
   // K%64!=0 dispatches to the p8 kernel upstream).
   const char* ep = getenv("LCTR_GEMM_APIPE");
   const int pipe = ep ? (ep[0] == '2' ? 2 : (ep[0] == '1' ? 1 : 0)) : 2;
+  *burst_out = burst;
+  if (K % G256_BK == 0)
+    *pipe_out = pipe;
+  else
+    *pipe_out = (ep && pipe) ? 1 : 0;  // only when explicitly requested
+}
+
+// burst, pipe as given; pipe 2 exists for full tiles only (K % 64 == 0),
+// the TAIL body takes pipe 0 or 1.
+void gemm256_bf16_launch_cfg(const void* A, const void* Bst,
+                             const float* bias, float* C, void* Cbf, int M,
+                             int N, int K, int act, bool burst, int pipe,
+                             hipStream_t stream) {
+  dim3 block(512);
+  dim3 grid(N / 256, M / 256);
 #define G256_LAUNCH(T, B, P)                                               \
   hipLaunchKernelGGL((gemm256_bf16_kernel<T, B, P>), grid, block, 0,       \
                      stream, (const __bf16*)A, (const __bf16*)Bst, bias,   \
@@ -334,7 +347,7 @@ void gemm256_bf16_launch(const void* A, const void* Bst, const float* bias,
       else G256_LAUNCH(false, false, 0);
     }
   } else {
-    const bool tail_pipe = ep && pipe;  // only when explicitly requested
+    const bool tail_pipe = pipe != 0;
     if (burst) {
       if (tail_pipe) G256_LAUNCH(true, true, 1);
       else G256_LAUNCH(true, true, 0);

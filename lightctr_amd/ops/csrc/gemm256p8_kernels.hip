@@ -104,9 +104,6 @@ __device__ __forceinline__ float p8_act(float v, int act) {
 // boundary) instead of the template's eight; the compiler pipelines the
 // phases freely as in the round-1 kernel. A/B lever for the big square
 // shapes where the 8-barrier variant measured 9% behind round 1.
-// DEEPA: A triple-buffered (3 parity slots, 160 KB LDS total) so A can
-// stage TWO tiles ahead like B; the boundary wait loosens from
-// vmcnt(4) to vmcnt(8) (one full tile of loads stays in flight).
 // APIPE (LCTR_GEMM_P8_APIPE=1, LITE only): phase-pipeline the per-phase
 // A-fragment ds_reads one MFMA cluster ahead through two named register
 // buffers, same transform as gemm256's LCTR_GEMM_APIPE (which measured
@@ -115,14 +112,13 @@ __device__ __forceinline__ float p8_act(float v, int act) {
 // before the previous phase's MFMA cluster is hazard-free; the LITE
 // mid-barrier constraint (B parity-slot overwrite) only orders b-frag
 // reads vs phase-2 staging and is preserved.
-template <bool TAIL, bool LITE, bool XCD, bool DEEPA = false,
-          bool APIPE = false>
+template <bool TAIL, bool LITE, bool XCD, bool APIPE = false>
 __global__ __launch_bounds__(512, 1) void gemm256p8_bf16_kernel(
     const __bf16* __restrict__ A, const __bf16* __restrict__ Bst,
     const float* __restrict__ bias, float* __restrict__ C,
     __bf16* __restrict__ Cbf, int M, int N, int K, int act) {
-  // LDS: A parity slots (2 or 3) then B parity 0/1 (16384 els each)
-  __shared__ __bf16 smem[(DEEPA ? 5 : 4) * 256 * P8_BK];
+  // LDS: A parity 0/1 then B parity 0/1 (16384 els each)
+  __shared__ __bf16 smem[4 * 256 * P8_BK];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int wm = wave >> 2;  // 0..1
@@ -152,13 +148,10 @@ __global__ __launch_bounds__(512, 1) void gemm256p8_bf16_kernel(
 
   __bf16* Abuf0 = smem;
   __bf16* Abuf1 = smem + 16384;
-  __bf16* Abuf2 = DEEPA ? smem + 2 * 16384 : nullptr;
-  __bf16* Bbuf0 = smem + (DEEPA ? 3 : 2) * 16384;
+  __bf16* Bbuf0 = smem + 2 * 16384;
   __bf16* Bbuf1 = Bbuf0 + 16384;
 
-#define P8_ABUF(tt)                                                        \
-  (DEEPA ? ((tt) % 3 == 0 ? Abuf0 : ((tt) % 3 == 1 ? Abuf1 : Abuf2))      \
-         : (((tt) & 1) ? Abuf1 : Abuf0))
+#define P8_ABUF(tt) (((tt) & 1) ? Abuf1 : Abuf0)
 #define P8_STAGE_A(tt, h)                                                   \
   do {                                                                      \
     __bf16* dst_ = P8_ABUF(tt) + (h) * 8192;                                \
@@ -178,22 +171,15 @@ __global__ __launch_bounds__(512, 1) void gemm256p8_bf16_kernel(
       p8_stage_half_tail(g_, K, krem, dst_);                                \
   } while (0)
 
-  // prologue: tile 0 (+ tile 1's B; DEEPA also tile 1's A) ahead
+  // prologue: tile 0 (+ tile 1's B) ahead
   P8_STAGE_A(0, 0);
   P8_STAGE_A(0, 1);
   P8_STAGE_B(0, 0);
   P8_STAGE_B(0, 1);
   if (NT > 1) {
-    if (DEEPA) {
-      P8_STAGE_A(1, 0);
-      P8_STAGE_A(1, 1);
-    }
     P8_STAGE_B(1, 0);
     P8_STAGE_B(1, 1);
-    if (DEEPA)
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
@@ -202,7 +188,7 @@ __global__ __launch_bounds__(512, 1) void gemm256p8_bf16_kernel(
   for (int t = 0; t < NT; ++t) {
     __bf16* curA = P8_ABUF(t);
     __bf16* curB = (t & 1) ? Bbuf1 : Bbuf0;
-    const bool sA = DEEPA ? (t + 2 < NT) : (t + 1 < NT);
+    const bool sA = t + 1 < NT;
     const bool sB = t + 2 < NT;
 
     // ---- phase 0: b-frags (whole tile) + A quadrant 0 ----
@@ -224,7 +210,7 @@ __global__ __launch_bounds__(512, 1) void gemm256p8_bf16_kernel(
         const int ks = kc * 32 + (lane >> 4) * 8;
         a[fm][kc] = *(const p8bf16x8*)&curA[ra * P8_BK + p8swz(ra, ks)];
       }
-    if (sA) P8_STAGE_A(DEEPA ? t + 2 : t + 1, 0);
+    if (sA) P8_STAGE_A(t + 1, 0);
 
 #define P8_READ_A_PH(P, ARR)                                             \
   _Pragma("unroll") for (int fm = 0; fm < 2; ++fm)                       \
@@ -247,7 +233,7 @@ __global__ __launch_bounds__(512, 1) void gemm256p8_bf16_kernel(
       p8bf16x8 a2[2][2];
       P8_READ_A_PH(1, a2);  // in flight under phase-0 MFMAs
       P8_MFMA_PH(0, a);
-      if (sA) P8_STAGE_A(DEEPA ? t + 2 : t + 1, 1);
+      if (sA) P8_STAGE_A(t + 1, 1);
       P8_READ_A_PH(2, a);
       P8_MFMA_PH(1, a2);
       // LITE mid-barrier: every wave is past its phase-0 MFMA issue
@@ -262,11 +248,7 @@ __global__ __launch_bounds__(512, 1) void gemm256p8_bf16_kernel(
       if (sB) P8_STAGE_B(t + 2, 1);
       P8_MFMA_PH(3, a2);
       // tile boundary: counted drain + publishing barrier (as below)
-      if (DEEPA && sA && sB)
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if (!DEEPA && sB)
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else if (DEEPA && sB)
+      if (sB)
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -304,7 +286,7 @@ __global__ __launch_bounds__(512, 1) void gemm256p8_bf16_kernel(
           a[fm][kc] = *(const p8bf16x8*)&curA[ra * P8_BK + p8swz(ra, ks)];
         }
       if (p == 1) {
-        if (sA) P8_STAGE_A(DEEPA ? t + 2 : t + 1, 1);
+        if (sA) P8_STAGE_A(t + 1, 1);
       } else if (p == 2) {
         if (sB) P8_STAGE_B(t + 2, 0);
       } else {
@@ -337,13 +319,9 @@ __global__ __launch_bounds__(512, 1) void gemm256p8_bf16_kernel(
         if constexpr (!LITE) __builtin_amdgcn_s_barrier();
       } else {
         // tile boundary: counted drain, then the barrier that publishes
-        // every wave's landed stages. DEEPA: A(t+2)+B(t+2) may stay in
-        // flight (vmcnt(8)); else only B(t+2) (vmcnt(4)).
-        if (DEEPA && sA && sB)
-          asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (!DEEPA && sB)
-          asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else if (DEEPA && sB)
+        // every wave's landed stages. Only B(t+2) may stay in flight
+        // (vmcnt(4)).
+        if (sB)
           asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -386,11 +364,8 @@ bool gemm256p8_eligible(int M, int N, int K, int transA, int transB) {
          K % 8 == 0 && K >= 32;
 }
 
-void gemm256p8_bf16_launch(const void* A, const void* Bst, const float* bias,
-                           float* C, void* Cbf, int M, int N, int K, int act,
-                           hipStream_t stream) {
-  dim3 block(512);
-  dim3 grid(N / 256, M / 256);
+// The environment's choice of body.
+void gemm256p8_default_cfg(bool* lite_out, bool* xcd_out, bool* apipe_out) {
   // LITE measured faster than the 8-barrier variant at every shape
   // (596 vs 555 TF on the W&D 65536x256x624 tail, 949 vs 904 @4k^3 —
   // profiles/r2_04_gemm_p8lite.txt): default on, =0 reverts.
@@ -402,17 +377,30 @@ void gemm256p8_bf16_launch(const void* A, const void* Bst, const float* bias,
     const char* e = getenv("LCTR_GEMM_P8_XCD");
     return e && e[0] == '1';
   }();
-  const bool tail = (K % P8_BK) != 0;
-  // phase-pipelined A reads (LITE only; A/B via LCTR_GEMM_P8_APIPE=0/1,
-  // re-read per launch for in-process sweeps)
+  // phase-pipelined A reads (LITE without XCD only; A/B via
+  // LCTR_GEMM_P8_APIPE=0/1, re-read per launch for in-process sweeps)
   const char* ea = getenv("LCTR_GEMM_P8_APIPE");
-  const bool apipe = ea && ea[0] == '1';
-#define P8_LAUNCH(T, L, X)                                                    hipLaunchKernelGGL((gemm256p8_bf16_kernel<T, L, X>), grid, block, 0,                           stream, (const __bf16*)A, (const __bf16*)Bst, bias, C,                      (__bf16*)Cbf, M, N, K, act)
-#define P8_LAUNCH_AP(T)                                                  \
-  hipLaunchKernelGGL((gemm256p8_bf16_kernel<T, true, false, false,       \
-                                            true>),                     \
-                     grid, block, 0, stream, (const __bf16*)A,           \
-                     (const __bf16*)Bst, bias, C, (__bf16*)Cbf, M, N, K, \
+  *lite_out = lite;
+  *xcd_out = xcd;
+  *apipe_out = ea && ea[0] == '1' && lite && !xcd;
+}
+
+// lite, xcd, apipe as given; apipe exists for lite without xcd only.
+void gemm256p8_bf16_launch_cfg(const void* A, const void* Bst,
+                               const float* bias, float* C, void* Cbf, int M,
+                               int N, int K, int act, bool lite, bool xcd,
+                               bool apipe, hipStream_t stream) {
+  dim3 block(512);
+  dim3 grid(N / 256, M / 256);
+  const bool tail = (K % P8_BK) != 0;
+#define P8_LAUNCH(T, L, X)                                                 \
+  hipLaunchKernelGGL((gemm256p8_bf16_kernel<T, L, X>), grid, block, 0,     \
+                     stream, (const __bf16*)A, (const __bf16*)Bst, bias,   \
+                     C, (__bf16*)Cbf, M, N, K, act)
+#define P8_LAUNCH_AP(T)                                                    \
+  hipLaunchKernelGGL((gemm256p8_bf16_kernel<T, true, false, true>), grid,  \
+                     block, 0, stream, (const __bf16*)A,                   \
+                     (const __bf16*)Bst, bias, C, (__bf16*)Cbf, M, N, K,   \
                      act)
   if (!tail && lite && !xcd && apipe) P8_LAUNCH_AP(false);
   else if (tail && lite && !xcd && apipe) P8_LAUNCH_AP(true);
@@ -429,3 +417,4 @@ void gemm256p8_bf16_launch(const void* A, const void* Bst, const float* bias,
 }
 
 }  // namespace lightctr
+

@@ -20,19 +20,13 @@
 //     AND dgrad hit the fast path; wgrad uses TRANSA=1 (+TRANSB=1)
 //   * fused epilogue: optional bias add + activation (relu/sigmoid) +
 //     optional bf16 mirror of C for the next layer's input.
+#include <cstdint>
+#include <cstdlib>
+
 #include "common.h"
 #include "launchers.h"
 
 namespace lightctr {
-
-bool gemm256_eligible(int M, int N, int K, int transA, int transB);
-void gemm256_bf16_launch(const void* A, const void* Bst, const float* bias,
-                         float* C, void* Cbf, int M, int N, int K, int act,
-                         hipStream_t stream);
-bool gemm256v2_eligible(int M, int N, int K, int transA, int transB);
-void gemm256v2_bf16_launch(const void* A, const void* Bst, const float* bias,
-                           float* C, void* Cbf, int M, int N, int K, int act,
-                           hipStream_t stream);
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -150,8 +144,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(
   const int N0 = blockIdx.x * GEMM_BN;
 
   // glds eligibility (full tile + 16B-aligned row stride + 16B base)
-  const bool a_glds = (TRANSA == 0) && (M0 + GEMM_BM <= M) && (K % 8 == 0);
-  const bool b_glds = (TRANSB == 0) && (N0 + GEMM_BN <= N) && (K % 8 == 0);
+  const bool a_glds = (TRANSA == 0) && (M0 + GEMM_BM <= M) && (K % 8 == 0) &&
+                      (((uintptr_t)A & 15) == 0);
+  const bool b_glds = (TRANSB == 0) && (N0 + GEMM_BN <= N) && (K % 8 == 0) &&
+                      (((uintptr_t)Bst & 15) == 0);
 
   f32x4 acc[4][4] = {};
 
@@ -217,95 +213,37 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(
   }
 }
 
-void gemm_bf16_launch(const void* A, const void* Bst, const float* bias,
-                      float* C, void* Cbf, int M, int N, int K, int transA,
-                      int transB, int act, hipStream_t stream) {
-  // v2 (counted-vmcnt k-chunk pipeline) measured 858/1026 TF vs v1's
-  // 992/1133 at 4k/8k^3: one barrier per 32-K chunk costs more than the
-  // barrier-spanning loads buy at this geometry. v1 stays preferred; v2
-  // kept (correct, race-screened) as the documented experiment.
-  if (gemm256p8_eligible(M, N, K, transA, transB)) {
-    // 8-phase counted-vmcnt schedule (round 2). Measured (gemm_p8/old.txt):
-    // 2x the round-1 kernel on K-tail shapes (65536x256x624: 555 vs 299
-    // TF — the masked-glds tail staging + counted waits), but ~8% behind
-    // it on big square K%64==0 shapes (904 vs 996 @4k^3) where the extra
-    // per-phase barriers outweigh the counted drain. Auto: p8 for tail
-    // shapes, round-1 kernel otherwise. LCTR_GEMM_P8=1/0 forces/disables.
-    static const int p8mode = [] {
-      const char* e = getenv("LCTR_GEMM_P8");
-      if (!e) return 2;  // auto
-      return e[0] == '0' ? 0 : 1;
-    }();
-    const bool use_p8 =
-        p8mode == 1 || (p8mode == 2 && (K % 64 != 0));
-    if (use_p8) {
-      gemm256p8_bf16_launch(A, Bst, bias, C, Cbf, M, N, K, act, stream);
-      return;
-    }
-  }
-  if (gemm256_eligible(M, N, K, transA, transB)) {
-    gemm256_bf16_launch(A, Bst, bias, C, Cbf, M, N, K, act, stream);
-    return;
-  }
-  if (gemm256n128_eligible(M, N, K, transA, transB)) {
-    gemm256n128_bf16_launch(A, Bst, bias, C, Cbf, M, N, K, act, stream);
-    return;
-  }
-  // degenerate shapes (the MLP's 1-wide output layer): direct kernels
-  // instead of 128x128 tiles at ~99% waste (see nn_kernels.hip)
-  if (N == 1 && transA == 0) {
-    gemv_n1_launch(A, Bst, bias, C, Cbf, M, K, act, stream);
-    return;
-  }
-  if (M == 1 && transA == 1 && transB == 1 && bias == nullptr &&
-      act == 0 && Cbf == nullptr) {
-    wrowsum_m1_launch(A, Bst, C, K, N, stream);
-    return;
-  }
-  // wgrad128 first: it beats small_wgrad even on tiny outputs
-  // (64x16x65536: 65 vs 93 us); small_wgrad keeps the shapes wgrad128
-  // cannot take (M or N not 16-aligned)
-  if (gemm_wgrad_eligible(M, N, K, transA, transB) && bias == nullptr &&
-      act == 0 && Cbf == nullptr) {
-    // K-major x K-major wgrad: linear glds staging + ds_read_b64_tr_b16
-    // cooperative-transpose fragment reads. Measured vs the generic
-    // scalar-transposed-staging path at K=65536: 256x512 67 vs 92 us,
-    // 128x256 40 vs 59, 256x624 (partial strip) 119 vs 126.
-    // LCTR_WGRAD128=0 reverts.
-    static const bool wg = [] {
-      const char* e = getenv("LCTR_WGRAD128");
-      return !(e && e[0] == '0');
-    }();
-    if (wg) {
-      gemm_wgrad_bf16_launch(A, Bst, C, M, N, K, stream);
-      return;
-    }
-  }
-  if (transA == 1 && transB == 1 && (long)M * N <= 4096 && K >= 8192 &&
-      bias == nullptr && act == 0 && Cbf == nullptr) {
-    small_wgrad_launch(A, Bst, C, M, N, K, stream);
-    return;
-  }
-  if (K == 1 && transA == 0) {
-    outer_k1_launch(A, Bst, bias, C, Cbf, M, N, act, stream);
-    return;
-  }
-  dim3 block(256);
-  dim3 grid((N + GEMM_BN - 1) / GEMM_BN, (M + GEMM_BM - 1) / GEMM_BM);
+// requested split-K fan-out -> K range per z-block (a multiple of the
+// K-tile, so only the last z-block can end on a partial tile)
+static int splitk_chunk(int K, int split_z) {
+  return ((K + split_z - 1) / split_z + GEMM_BK - 1) / GEMM_BK * GEMM_BK;
+}
+
+int gemm_generic_default_split(int M, int N, int K, bool plain) {
   // split-K when the output grid is far too small to fill 256 CUs and K is
   // deep (the wgrad regime): target >= 512 z*xy blocks
+  const long xy = (long)((N + GEMM_BN - 1) / GEMM_BN) *
+                  ((M + GEMM_BM - 1) / GEMM_BM);
+  if (!(xy < 64 && K >= 4096 && plain)) return 0;
+  // split-K fan-out target (blocks in flight); LCTR_SPLITK_TARGET
+  // overrides for sweeps
+  static const int sk_target = [] {
+    const char* e = getenv("LCTR_SPLITK_TARGET");
+    return e ? atoi(e) : 512;
+  }();
+  return min(64, max(2, sk_target / (int)xy));
+}
+
+void gemm_generic_bf16_launch_cfg(const void* A, const void* Bst,
+                                  const float* bias, float* C, void* Cbf,
+                                  int M, int N, int K, int transA,
+                                  int transB, int act, int split_z,
+                                  hipStream_t stream) {
+  dim3 block(256);
+  dim3 grid((N + GEMM_BN - 1) / GEMM_BN, (M + GEMM_BM - 1) / GEMM_BM);
   int kchunk = 0;
-  const int xy = (int)(grid.x * grid.y);
-  if (xy < 64 && K >= 4096 && Cbf == nullptr && bias == nullptr &&
-      act == 0) {
-    // split-K fan-out target (blocks in flight); LCTR_SPLITK_TARGET
-    // overrides for sweeps
-    static const int sk_target = [] {
-      const char* e = getenv("LCTR_SPLITK_TARGET");
-      return e ? atoi(e) : 512;
-    }();
-    int zw = min(64, max(2, sk_target / xy));
-    kchunk = ((K + zw - 1) / zw + GEMM_BK - 1) / GEMM_BK * GEMM_BK;
+  if (split_z > 0) {  // caller guarantees no bias / act / Cbf
+    kchunk = splitk_chunk(K, split_z);
     grid.z = (K + kchunk - 1) / kchunk;
     LCTR_CHECK_HIP(hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float),
                                   stream));
@@ -321,4 +259,144 @@ void gemm_bf16_launch(const void* A, const void* Bst, const float* bias,
 #undef LAUNCH_GEMM
 }
 
+// The default dispatch, as a decision only. `aligned16`: both operand base
+// addresses are 16 B-aligned; every glds / vector-load body needs that, so
+// an offset view goes to the bodies that load element by element.
+GemmRoute gemm_bf16_pick(int M, int N, int K, int transA, int transB,
+                         bool has_bias, int act, bool has_cbf,
+                         bool aligned16) {
+  GemmRoute r;
+  const bool plain = !has_bias && act == 0 && !has_cbf;
+  // v2 (counted-vmcnt k-chunk pipeline) measured 858/1026 TF vs v1's
+  // 992/1133 at 4k/8k^3: one barrier per 32-K chunk costs more than the
+  // barrier-spanning loads buy at this geometry. v1 stays preferred; v2
+  // is never picked here and is reached through gemm_bf16_variant only.
+  if (aligned16 && gemm256p8_eligible(M, N, K, transA, transB)) {
+    // 8-phase counted-vmcnt schedule (round 2). Measured (gemm_p8/old.txt):
+    // 2x the round-1 kernel on K-tail shapes (65536x256x624: 555 vs 299
+    // TF — the masked-glds tail staging + counted waits), but ~8% behind
+    // it on big square K%64==0 shapes (904 vs 996 @4k^3) where the extra
+    // per-phase barriers outweigh the counted drain. Auto: p8 for tail
+    // shapes, round-1 kernel otherwise. LCTR_GEMM_P8=1/0 forces/disables.
+    static const int p8mode = [] {
+      const char* e = getenv("LCTR_GEMM_P8");
+      if (!e) return 2;  // auto
+      return e[0] == '0' ? 0 : 1;
+    }();
+    const bool use_p8 =
+        p8mode == 1 || (p8mode == 2 && (K % 64 != 0));
+    if (use_p8) {
+      r.body = GEMM_BODY_P8;
+      gemm256p8_default_cfg(&r.lite, &r.xcd, &r.apipe);
+      return r;
+    }
+  }
+  if (aligned16 && gemm256_eligible(M, N, K, transA, transB)) {
+    r.body = GEMM_BODY_256;
+    gemm256_default_cfg(K, &r.burst, &r.pipe);
+    return r;
+  }
+  if (aligned16 && gemm256n128_eligible(M, N, K, transA, transB)) {
+    r.body = GEMM_BODY_N128;
+    return r;
+  }
+  // degenerate shapes (the MLP's 1-wide output layer): direct kernels
+  // instead of 128x128 tiles at ~99% waste (see nn_kernels.hip)
+  if (N == 1 && transA == 0) {
+    r.body = GEMM_BODY_GEMV_N1;
+    return r;
+  }
+  if (M == 1 && transA == 1 && transB == 1 && plain) {
+    r.body = GEMM_BODY_WROWSUM_M1;
+    return r;
+  }
+  // wgrad128 first: it beats small_wgrad even on tiny outputs
+  // (64x16x65536: 65 vs 93 us); small_wgrad keeps the shapes wgrad128
+  // cannot take (M or N not 16-aligned)
+  if (aligned16 && gemm_wgrad_eligible(M, N, K, transA, transB) && plain) {
+    // K-major x K-major wgrad: linear glds staging + ds_read_b64_tr_b16
+    // cooperative-transpose fragment reads. Measured vs the generic
+    // scalar-transposed-staging path at K=65536: 256x512 67 vs 92 us,
+    // 128x256 40 vs 59, 256x624 (partial strip) 119 vs 126.
+    // LCTR_WGRAD128=0 reverts.
+    static const bool wg = [] {
+      const char* e = getenv("LCTR_WGRAD128");
+      return !(e && e[0] == '0');
+    }();
+    if (wg) {
+      r.body = GEMM_BODY_WGRAD128;
+      r.split_z = gemm_wgrad_default_split(M, N, K);
+      return r;
+    }
+  }
+  if (transA == 1 && transB == 1 && (long)M * N <= 4096 && K >= 8192 &&
+      plain) {
+    r.body = GEMM_BODY_SMALL_WGRAD;
+    return r;
+  }
+  if (K == 1 && transA == 0) {
+    r.body = GEMM_BODY_OUTER_K1;
+    return r;
+  }
+  r.body = GEMM_BODY_GENERIC;
+  r.split_z = gemm_generic_default_split(M, N, K, plain);
+  return r;
+}
+
+// Launch the body a route names. The caller (the default dispatch above,
+// or gemm_bf16_variant after its own checks) guarantees the body accepts
+// the shape, layout, epilogue and operand alignment.
+void gemm_bf16_run(const GemmRoute& r, const void* A, const void* Bst,
+                   const float* bias, float* C, void* Cbf, int M, int N,
+                   int K, int transA, int transB, int act,
+                   hipStream_t stream) {
+  switch (r.body) {
+    case GEMM_BODY_P8:
+      gemm256p8_bf16_launch_cfg(A, Bst, bias, C, Cbf, M, N, K, act, r.lite,
+                                r.xcd, r.apipe, stream);
+      return;
+    case GEMM_BODY_256:
+      gemm256_bf16_launch_cfg(A, Bst, bias, C, Cbf, M, N, K, act, r.burst,
+                              r.pipe, stream);
+      return;
+    case GEMM_BODY_V2:
+      gemm256v2_bf16_launch(A, Bst, bias, C, Cbf, M, N, K, act, stream);
+      return;
+    case GEMM_BODY_N128:
+      gemm256n128_bf16_launch(A, Bst, bias, C, Cbf, M, N, K, act, stream);
+      return;
+    case GEMM_BODY_GEMV_N1:
+      gemv_n1_launch(A, Bst, bias, C, Cbf, M, K, act, stream);
+      return;
+    case GEMM_BODY_WROWSUM_M1:
+      wrowsum_m1_launch(A, Bst, C, K, N, stream);
+      return;
+    case GEMM_BODY_WGRAD128:
+      gemm_wgrad_bf16_launch_cfg(A, Bst, C, M, N, K, r.split_z, stream);
+      return;
+    case GEMM_BODY_SMALL_WGRAD:
+      small_wgrad_launch(A, Bst, C, M, N, K, stream);
+      return;
+    case GEMM_BODY_OUTER_K1:
+      outer_k1_launch(A, Bst, bias, C, Cbf, M, N, act, stream);
+      return;
+    default:
+      gemm_generic_bf16_launch_cfg(A, Bst, bias, C, Cbf, M, N, K, transA,
+                                   transB, act, r.split_z, stream);
+      return;
+  }
+}
+
+void gemm_bf16_launch(const void* A, const void* Bst, const float* bias,
+                      float* C, void* Cbf, int M, int N, int K, int transA,
+                      int transB, int act, hipStream_t stream) {
+  const bool aligned16 = (((uintptr_t)A | (uintptr_t)Bst) & 15) == 0;
+  const GemmRoute r =
+      gemm_bf16_pick(M, N, K, transA, transB, bias != nullptr, act,
+                     Cbf != nullptr, aligned16);
+  gemm_bf16_run(r, A, Bst, bias, C, Cbf, M, N, K, transA, transB, act,
+                stream);
+}
+
 }  // namespace lightctr
+

@@ -223,28 +223,41 @@ bool gemm_wgrad_eligible(int M, int N, int K, int transA, int transB) {
          K >= 1024;
 }
 
-void gemm_wgrad_bf16_launch(const void* At, const void* Bt, float* C, int M,
-                            int N, int K, hipStream_t stream) {
-  dim3 block(256);
-  dim3 grid((N + WG_BN - 1) / WG_BN, (M + WG_BM - 1) / WG_BM);
-  int kchunk = 0;
-  const int xy = (int)(grid.x * grid.y);
+// The default split-K fan-out (0 = one block per output tile).
+int gemm_wgrad_default_split(int M, int N, int K) {
+  const int xy = ((N + WG_BN - 1) / WG_BN) * ((M + WG_BM - 1) / WG_BM);
   static const int sk_target = [] {
     const char* e = getenv("LCTR_SPLITK_TARGET");
     return e ? atoi(e) : 512;
   }();
   if (xy < 256 && K >= 2048) {
-    int zw = min(64, max(1, sk_target / xy));
-    if (zw > 1) {
-      kchunk = ((K + zw - 1) / zw + WG_BK - 1) / WG_BK * WG_BK;
-      grid.z = (K + kchunk - 1) / kchunk;
-      LCTR_CHECK_HIP(
-          hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), stream));
-    }
+    const int zw = min(64, max(1, sk_target / xy));
+    if (zw > 1) return zw;
+  }
+  return 0;
+}
+
+void gemm_wgrad_bf16_launch_cfg(const void* At, const void* Bt, float* C,
+                                int M, int N, int K, int split_z,
+                                hipStream_t stream) {
+  dim3 block(256);
+  dim3 grid((N + WG_BN - 1) / WG_BN, (M + WG_BM - 1) / WG_BM);
+  int kchunk = 0;
+  if (split_z > 0) {
+    kchunk = ((K + split_z - 1) / split_z + WG_BK - 1) / WG_BK * WG_BK;
+    grid.z = (K + kchunk - 1) / kchunk;
+    LCTR_CHECK_HIP(
+        hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), stream));
   }
   hipLaunchKernelGGL(gemm_wgrad_bf16_kernel, grid, block, 0, stream,
                      (const __bf16*)At, (const __bf16*)Bt, C, M, N, K,
                      kchunk);
+}
+
+void gemm_wgrad_bf16_launch(const void* At, const void* Bt, float* C, int M,
+                            int N, int K, hipStream_t stream) {
+  gemm_wgrad_bf16_launch_cfg(At, Bt, C, M, N, K,
+                             gemm_wgrad_default_split(M, N, K), stream);
 }
 
 }  // namespace lightctr

@@ -156,28 +156,81 @@ void fm_ftrl_apply_launch(const int* uniq, const int* count, float* W,
 
 // --- gemm_wgrad_kernels.hip ---
 bool gemm_wgrad_eligible(int M, int N, int K, int transA, int transB);
+// split_z: requested split-K fan-out, 0 = one block per output tile
+int gemm_wgrad_default_split(int M, int N, int K);
+void gemm_wgrad_bf16_launch_cfg(const void* At, const void* Bt, float* C,
+                                int M, int N, int K, int split_z,
+                                ihipStream_t* stream);
 void gemm_wgrad_bf16_launch(const void* At, const void* Bt, float* C, int M,
                             int N, int K, ihipStream_t* stream);
 void wg_probe_launch(const void* g, int ld, void* out_lds, float* out_frag,
                      int mode, ihipStream_t* stream);
 
 // --- gemm_kernels.hip ---
+// Every GEMM launcher comes in two parts: `*_launch_cfg` takes the body's
+// configuration explicitly (the K-tail flag alone is derived from K), and
+// `*_default_cfg` / `*_default_split` give the environment's choice (knobs
+// read once per process into function-local statics; the APIPE knobs per
+// call). The default dispatch is gemm_bf16_pick, which asks the latter,
+// then gemm_bf16_run, which calls the former.
+enum GemmBody {
+  GEMM_BODY_GENERIC = 0,
+  GEMM_BODY_256,
+  GEMM_BODY_P8,
+  GEMM_BODY_V2,
+  GEMM_BODY_N128,
+  GEMM_BODY_WGRAD128,
+  GEMM_BODY_GEMV_N1,
+  GEMM_BODY_WROWSUM_M1,
+  GEMM_BODY_SMALL_WGRAD,
+  GEMM_BODY_OUTER_K1,
+};
+struct GemmRoute {
+  int body = GEMM_BODY_GENERIC;
+  int split_z = 0;     // generic / wgrad128: split-K fan-out, 0 = none
+  int pipe = 0;        // gemm256: A-read schedule 0 / 1 / 2
+  bool burst = false;  // gemm256
+  bool lite = true;    // p8: 2 barriers per K-tile (false: 8)
+  bool xcd = false;    // p8: XCD tile remap
+  bool apipe = false;  // p8: pipelined A reads (lite, no xcd)
+};
+GemmRoute gemm_bf16_pick(int M, int N, int K, int transA, int transB,
+                         bool has_bias, int act, bool has_cbf,
+                         bool aligned16);
+void gemm_bf16_run(const GemmRoute& r, const void* A, const void* Bst,
+                   const float* bias, float* C, void* Cbf, int M, int N,
+                   int K, int transA, int transB, int act,
+                   ihipStream_t* stream);
 void gemm_bf16_launch(const void* A, const void* Bst, const float* bias,
                       float* C, void* Cbf, int M, int N, int K, int transA,
                       int transB, int act, ihipStream_t* stream);
+int gemm_generic_default_split(int M, int N, int K, bool plain);
+void gemm_generic_bf16_launch_cfg(const void* A, const void* Bst,
+                                  const float* bias, float* C, void* Cbf,
+                                  int M, int N, int K, int transA,
+                                  int transB, int act, int split_z,
+                                  ihipStream_t* stream);
 
 bool gemm256_eligible(int M, int N, int K, int transA, int transB);
+void gemm256_default_cfg(int K, bool* burst, int* pipe);
+void gemm256_bf16_launch_cfg(const void* A, const void* Bst,
+                             const float* bias, float* C, void* Cbf, int M,
+                             int N, int K, int act, bool burst, int pipe,
+                             ihipStream_t* stream);
 bool gemm256p8_eligible(int M, int N, int K, int transA, int transB);
-void gemm256p8_bf16_launch(const void* A, const void* Bst, const float* bias,
+void gemm256p8_default_cfg(bool* lite, bool* xcd, bool* apipe);
+void gemm256p8_bf16_launch_cfg(const void* A, const void* Bst,
+                               const float* bias, float* C, void* Cbf, int M,
+                               int N, int K, int act, bool lite, bool xcd,
+                               bool apipe, ihipStream_t* stream);
+bool gemm256v2_eligible(int M, int N, int K, int transA, int transB);
+void gemm256v2_bf16_launch(const void* A, const void* Bst, const float* bias,
                            float* C, void* Cbf, int M, int N, int K, int act,
                            ihipStream_t* stream);
 bool gemm256n128_eligible(int M, int N, int K, int transA, int transB);
 void gemm256n128_bf16_launch(const void* A, const void* Bst,
                              const float* bias, float* C, void* Cbf, int M,
                              int N, int K, int act, ihipStream_t* stream);
-void gemm256_bf16_launch(const void* A, const void* Bst, const float* bias,
-                         float* C, void* Cbf, int M, int N, int K, int act,
-                         ihipStream_t* stream);
 
 // --- nn_kernels.hip ---
 void small_wgrad_launch(const void* Ast, const void* Bst, float* C, int M,

@@ -239,7 +239,10 @@ def test_gemm_sigmoid_epilogue_and_256path_bf16_emit():
 @pytest.mark.gpu
 def test_gemm_v2_race_screen():
     """Sync-structure kernels need multi-run race screens (guide two-lane
-    discipline): 10 repeated runs of a v2-routed shape must all match."""
+    discipline): 10 repeated runs of a v2-eligible shape through the
+    default dispatch (which picks the round-1 gemm256 kernel for it), then
+    10 runs of the v2 kernel itself through gemm_bf16_variant, must all
+    match."""
     from lightctr_amd.ops import hip_ops
 
     M, N, K = 2048, 2048, 2048
@@ -251,6 +254,12 @@ def test_gemm_v2_race_screen():
         C = hip_ops.gemm_bf16(A, Bst, None, M, N, K, 0, 0, 0, False)
         assert torch.allclose(C, ref, atol=2e-2 * K ** 0.5, rtol=1e-2), \
             (it, (C - ref).abs().max())
+    assert hip_ops.gemm_bf16_route(M, N, K, 0, 0, False, 0, False) != "v2"
+    for it in range(10):
+        C, = hip_ops.gemm_bf16_variant(A, Bst, None, M, N, K, 0, 0, 0, False,
+                                       "v2", 0)
+        assert torch.allclose(C, ref, atol=2e-2 * K ** 0.5, rtol=1e-2), \
+            ("v2", it, (C - ref).abs().max())
 
 
 @pytest.mark.gpu
