@@ -12,6 +12,7 @@ command:
         --data dense.csv ...      (dense rows; served by the compiled forest)
     python -m lightctr_amd.cli neighbors --load emb.pt --words a0,b1 \
         --topk 5 [--index pq --pq-sub 4 --rerank 32]
+        [--index forest --trees 8 --leaf-size 16 --search-k 160]
 
 Distributed modes are launched via torch.distributed.run (one rank per
 GPU), selecting --mode ring|sharded|ps at runtime.
@@ -448,6 +449,11 @@ def cmd_neighbors(args) -> int:
         kw = {"n_sub": args.pq_sub, "seed": args.seed}
         if args.rerank:
             skw = {"rerank": args.rerank}
+    elif args.index == "forest":
+        kw = {"n_trees": args.trees, "leaf_size": args.leaf_size,
+              "seed": args.seed}
+        if args.search_k:
+            skw = {"search_k": args.search_k}
     m.build_index(kind=args.index, **kw)  # cosine ranking
     res = m.neighbors(words, args.topk, **skw)
     print(json.dumps({"index": args.index,
@@ -464,9 +470,15 @@ def build_parser():
     p.add_argument("--load", default=None, help="file of train --model embed")
     p.add_argument("--words", required=True, help="comma-separated words")
     p.add_argument("--topk", type=int, default=5)
-    p.add_argument("--index", default="flat", choices=("flat", "pq"))
+    p.add_argument("--index", default="flat",
+                   choices=("flat", "pq", "forest"))
     p.add_argument("--pq-sub", type=int, default=4)
     p.add_argument("--rerank", type=int, default=0)
+    p.add_argument("--trees", type=int, default=8)
+    p.add_argument("--leaf-size", type=int, default=16)
+    p.add_argument("--search-k", type=int, default=0,
+                   help="ids the forest gathers per query "
+                        "(0: 2 * trees * (topk + 1))")
     p.add_argument("--device", default=None)
     p.add_argument("--seed", type=int, default=0)
     for name, fn in (("train", cmd_train), ("predict", cmd_predict)):

@@ -217,10 +217,12 @@ class EmbedModel:
 
     def build_index(self, kind: str = "flat", metric: str = "ip", **kw):
         """Index the table for batched search (predict/knn.py): ``flat``
-        is exact, ``pq`` takes PQIndex.build's keywords (n_sub, ...). For
+        is exact, ``pq`` takes PQIndex.build's keywords (n_sub, ...),
+        ``forest`` ForestIndex.build's (n_trees, leaf_size, seed). For
         ``ip`` a unit-length copy of E is indexed, so the ranking is the
         cosine ranking of ``most_similar``. Rebuild after more training."""
         from ..predict.knn import FlatIndex, PQIndex
+        from ..predict.rp_forest import ForestIndex
 
         E = self.E
         if metric == "ip":
@@ -231,8 +233,11 @@ class EmbedModel:
         elif kind == "pq":
             kw.setdefault("n_sub", 4)
             index = PQIndex.build(E, metric=metric, **kw)
+        elif kind == "forest":
+            index = ForestIndex.build(E, metric=metric, **kw)
         else:
-            raise ValueError(f"kind must be 'flat' or 'pq', got {kind!r}")
+            raise ValueError(f"kind must be 'flat', 'pq' or 'forest', "
+                             f"got {kind!r}")
         self._index, self._index_vectors = index, E
         return index
 

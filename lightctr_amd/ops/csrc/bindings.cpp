@@ -1612,6 +1612,58 @@ std::vector<at::Tensor> flat_topk(at::Tensor X, at::Tensor Q, int64_t metric,
   return out;
 }
 
+// ---- random-projection forest (predict/rp_forest.py) ----
+
+at::Tensor forest_candidates(at::Tensor planes, at::Tensor bias,
+                             at::Tensor child, at::Tensor roots,
+                             at::Tensor leaf_off, at::Tensor leaf_items,
+                             at::Tensor Q, int64_t search_k, int64_t width) {
+  check_cuda_f32(planes, "planes");
+  check_cuda_f32(bias, "bias");
+  check_cuda_i32(child, "child");
+  check_cuda_i32(roots, "roots");
+  check_cuda_i32(leaf_off, "leaf_off");
+  check_cuda_i32(leaf_items, "leaf_items");
+  check_cuda_f32(Q, "Q");
+  CHK(planes.dim() == 2 && Q.dim() == 2,
+      "planes must be [n_inner, dim], Q [nq, dim]");
+  const int64_t n_inner = planes.size(0), dim = planes.size(1),
+                nq = Q.size(0), T = roots.numel(),
+                total = leaf_items.numel();
+  CHK(dim >= 1 && dim <= lightctr::knn_max_dim(), "dim must be in [1, ",
+      lightctr::knn_max_dim(), "], got ", dim);
+  CHK(Q.size(1) == dim, "Q has ", Q.size(1), " columns, the planes have ",
+      dim);
+  CHK(bias.dim() == 1 && bias.size(0) == n_inner, "bias must be [n_inner]");
+  CHK(child.dim() == 2 && child.size(0) == n_inner && child.size(1) == 2,
+      "child must be [n_inner, 2]");
+  CHK(roots.dim() == 1 && T >= 1, "roots must be [T] with T >= 1");
+  CHK(leaf_off.dim() == 1 && leaf_off.numel() >= 1,
+      "leaf_off must be [n_leaves + 1]");
+  CHK(leaf_items.dim() == 1, "leaf_items must be [total]");
+  const int64_t n_leaves = leaf_off.numel() - 1;
+  const int64_t lim = ((int64_t)1 << 31) - 1;
+  CHK(n_inner <= lim && n_leaves < lim && T <= lim && total <= lim,
+      "forest arrays must hold fewer than 2^31 entries");
+  CHK(search_k >= 1 && search_k <= lightctr::forest_max_search(),
+      "search_k must be in [1, ", lightctr::forest_max_search(), "], got ",
+      search_k);
+  CHK(width >= search_k, "width ", width, " is below search_k ", search_k);
+  CHK(width < ((int64_t)1 << 31) && nq * width < ((int64_t)1 << 40),
+      "candidate list too large");
+  CHK((nq + 3) / 4 < ((int64_t)1 << 31), "too many blocks");
+  auto cand = at::empty({nq, width}, Q.options().dtype(at::kInt));
+  if (nq == 0) return cand;
+  lightctr::forest_candidates_launch(
+      planes.data_ptr<float>(), bias.data_ptr<float>(), child.data_ptr<int>(),
+      roots.data_ptr<int>(), leaf_off.data_ptr<int>(),
+      leaf_items.data_ptr<int>(), Q.data_ptr<float>(), cand.data_ptr<int>(),
+      (long)nq, (int)dim, (int)n_inner, (int)n_leaves, (int)T, (long)total,
+      (int)search_k, (long)width, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return cand;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1815,4 +1867,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("knn_slice_rows", &lightctr::knn_slice_rows,
         "rows per block slice for n rows and nq queries", py::arg("n"),
         py::arg("nq"));
+  m.def("forest_candidates", &forest_candidates,
+        "best-first walk of a flattened random-projection forest -> "
+        "candidate ids int32 [nq, width], -1 padded",
+        py::arg("planes"), py::arg("bias"), py::arg("child"),
+        py::arg("roots"), py::arg("leaf_off"), py::arg("leaf_items"),
+        py::arg("Q"), py::arg("search_k"), py::arg("width"));
+  m.def("forest_queue", &lightctr::forest_queue,
+        "queue entries per query of forest_candidates");
+  m.def("forest_max_search", &lightctr::forest_max_search,
+        "largest search_k of forest_candidates");
 }

@@ -469,4 +469,201 @@ void flat_topk_launch(const float* X, long stride, long N, int dim,
 #undef KNN_FLAT
 }
 
+// ---- random-projection forest: candidate lists (predict/rp_forest.py) ----
+//
+// One wavefront walks the whole forest for one query with a best-first
+// queue of (bound, code) entries; a code is an inner node i >= 0 or
+// -1 - l for leaf l. Queue order: larger bound first (float `<`, so -0 and
+// +0 tie), ties to the lower signed code. An entry is one 64-bit key, high
+// word -bound through knn_make_key's float mapping, low word code ^ 2^31,
+// so the unsigned key order is the queue order and the first entry is the
+// smallest key. The queue is an unordered array of FOREST_QUEUE keys per
+// wave in LDS: pop is a wave-wide min over the live prefix (the last entry
+// fills the hole), a push into a full queue is a wave-wide max and replace.
+// The query sits in registers, lane-strided; a plane row is read coalesced
+// and reduced with a fixed shuffle tree, the bias is added last. Every
+// queue decision is taken from values every lane holds alike; there are no
+// atomics, and no block barrier (waves of a block share nothing).
+//
+// Guards for a malformed forest: every code read from memory is
+// range-checked before it is queued, leaf bounds before they are used, the
+// pop loop runs at most n_inner + n_leaves + T times and every store is
+// inside the row of `width` slots.
+
+#define FOREST_WAVES (KNN_BLOCK / LCTR_WAVE)
+#define FOREST_QUEUE 1024
+#define FOREST_MAX_SEARCH 65536
+#define FOREST_QREGS (KNN_MAX_DIM / LCTR_WAVE)
+
+__device__ __forceinline__ knn_key_t forest_key(float bound, int code) {
+  return knn_make_key(-bound, (int)((unsigned)code ^ 0x80000000u));
+}
+
+// orders one lane's LDS writes before the other lanes' reads (same wave)
+__device__ __forceinline__ void forest_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// wave-wide min or max of 64-bit keys; every lane gets the same key
+template <bool MAX>
+__device__ __forceinline__ knn_key_t forest_wave_extreme(knn_key_t v) {
+#pragma unroll
+  for (int s = 1; s < LCTR_WAVE; s <<= 1) {
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, s);
+    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), s);
+    const knn_key_t o = ((knn_key_t)hi << 32) | lo;
+    v = MAX ? (o > v ? o : v) : (o < v ? o : v);
+  }
+  return v;
+}
+
+__device__ __forceinline__ int forest_uniform(int v) {
+  return __builtin_amdgcn_readfirstlane(v);
+}
+
+// the lowest lane whose flag is set (one is)
+__device__ __forceinline__ int forest_first_lane(bool flag) {
+  return __ffsll((unsigned long long)__ballot(flag)) - 1;
+}
+
+__device__ __forceinline__ void forest_push(knn_key_t* qu, int& n,
+                                            knn_key_t key, int lane) {
+  if (n < FOREST_QUEUE) {
+    if (lane == 0) qu[n] = key;
+    ++n;
+  } else {
+    // full: whichever of the FOREST_QUEUE + 1 entries is last goes
+    knn_key_t worst = 0;
+    int slot = lane;
+    for (int j = lane; j < FOREST_QUEUE; j += LCTR_WAVE) {
+      const knn_key_t e = qu[j];
+      if (e >= worst) {
+        worst = e;
+        slot = j;
+      }
+    }
+    const knn_key_t w = forest_wave_extreme<true>(worst);
+    const int owner = forest_first_lane(worst == w);
+    if (key < w && lane == owner) qu[slot] = key;
+  }
+  forest_wave_sync();
+}
+
+// removes and returns the first entry of a queue of n >= 1 entries
+__device__ __forceinline__ knn_key_t forest_pop(knn_key_t* qu, int& n,
+                                                int lane) {
+  knn_key_t best = KNN_PAD;
+  int slot = 0;
+  for (int j = lane; j < n; j += LCTR_WAVE) {
+    const knn_key_t e = qu[j];
+    if (e <= best) {
+      best = e;
+      slot = j;
+    }
+  }
+  const knn_key_t b = forest_wave_extreme<false>(best);
+  const int owner = forest_first_lane(best == b && lane < n);
+  const int hole = __shfl(slot, owner);
+  const knn_key_t last = qu[n - 1];
+  forest_wave_sync();  // everyone has read the queue
+  --n;
+  if (lane == 0 && hole < n) qu[hole] = last;
+  forest_wave_sync();
+  return b;
+}
+
+__device__ __forceinline__ bool forest_code_ok(int c, int n_inner,
+                                               int n_leaves) {
+  return c >= 0 ? c < n_inner : -1 - c < n_leaves;
+}
+
+__global__ __launch_bounds__(KNN_BLOCK) void forest_candidates_kernel(
+    const float* __restrict__ planes, const float* __restrict__ bias,
+    const int* __restrict__ child, const int* __restrict__ roots,
+    const int* __restrict__ leaf_off, const int* __restrict__ leaf_items,
+    const float* __restrict__ Q, int* __restrict__ cand, long nq, int dim,
+    int n_inner, int n_leaves, int T, long total, int search_k, long width) {
+  __shared__ knn_key_t s_queue[FOREST_WAVES][FOREST_QUEUE];
+  const int lane = threadIdx.x % LCTR_WAVE;
+  const int wave = forest_uniform(threadIdx.x / LCTR_WAVE);
+  const long q = (long)blockIdx.x * FOREST_WAVES + wave;
+  if (q >= nq) return;
+  knn_key_t* qu = s_queue[wave];
+  int* row = cand + q * width;
+
+  float qr[FOREST_QREGS];
+#pragma unroll
+  for (int r = 0; r < FOREST_QREGS; ++r) {
+    const int j = lane + r * LCTR_WAVE;
+    qr[r] = j < dim ? Q[q * dim + j] : 0.f;
+  }
+
+  int n = 0;
+  const float inf = __uint_as_float(0x7f800000u);
+  for (int t = 0; t < T; ++t) {
+    const int c = roots[t];
+    if (forest_code_ok(c, n_inner, n_leaves))
+      forest_push(qu, n, forest_key(inf, c), lane);
+  }
+
+  long written = 0;
+  long budget = (long)n_inner + n_leaves + T;
+  while (n > 0 && written < search_k && budget-- > 0) {
+    const knn_key_t key = forest_pop(qu, n, lane);
+    const unsigned klo = (unsigned)forest_uniform((int)(unsigned)key);
+    const unsigned khi = (unsigned)forest_uniform((int)(unsigned)(key >> 32));
+    const float bound = -knn_key_dist((knn_key_t)khi << 32);
+    const int code = (int)(klo ^ 0x80000000u);
+    if (code < 0) {
+      const int l = -1 - code;
+      const long beg = leaf_off[l], end = leaf_off[l + 1];
+      if (beg < 0 || end < beg || end > total) continue;
+      for (long j = lane; j < end - beg; j += LCTR_WAVE)
+        if (written + j < width) row[written + j] = leaf_items[beg + j];
+      written += end - beg;
+    } else {
+      const float* p = planes + (long)code * dim;
+      const int c0 = child[2 * (long)code], c1 = child[2 * (long)code + 1];
+      const float bi = bias[code];
+      float acc = 0.f;
+#pragma unroll
+      for (int r = 0; r < FOREST_QREGS; ++r) {
+        if (r * LCTR_WAVE >= dim) break;
+        const int j = lane + r * LCTR_WAVE;
+        if (j < dim) acc += p[j] * qr[r];
+      }
+      float m = wave_reduce_sum(acc) + bi;
+      m = __uint_as_float((unsigned)forest_uniform((int)__float_as_uint(m)));
+      const float am = fabsf(m);
+      const int near = m > 0.f ? c0 : c1, far = m > 0.f ? c1 : c0;
+      if (forest_code_ok(near, n_inner, n_leaves))
+        forest_push(qu, n, forest_key(fminf(bound, am), near), lane);
+      if (forest_code_ok(far, n_inner, n_leaves))
+        forest_push(qu, n, forest_key(fminf(bound, -am), far), lane);
+    }
+  }
+  for (long j = written + lane; j < width; j += LCTR_WAVE) row[j] = -1;
+}
+
+int forest_queue() { return FOREST_QUEUE; }
+int forest_max_search() { return FOREST_MAX_SEARCH; }
+
+// cand is [nq, width] int32; the forest arrays are those of
+// predict/rp_forest.py (child is [n_inner, 2])
+void forest_candidates_launch(const float* planes, const float* bias,
+                              const int* child, const int* roots,
+                              const int* leaf_off, const int* leaf_items,
+                              const float* Q, int* cand, long nq, int dim,
+                              int n_inner, int n_leaves, int T, long total,
+                              int search_k, long width, hipStream_t stream) {
+  if (nq <= 0) return;
+  const long blocks = (nq + FOREST_WAVES - 1) / FOREST_WAVES;
+  hipLaunchKernelGGL(forest_candidates_kernel, dim3((unsigned)blocks),
+                     dim3(KNN_BLOCK), 0, stream, planes, bias, child, roots,
+                     leaf_off, leaf_items, Q, cand, nq, dim, n_inner,
+                     n_leaves, T, total, search_k, width);
+}
+
 }  // namespace lightctr

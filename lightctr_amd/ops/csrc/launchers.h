@@ -372,5 +372,16 @@ void flat_topk_launch(const float* X, long stride, long N, int dim,
                       ihipStream_t* stream);
 void knn_merge_launch(const void* partial, long nq, int n_slices, int k,
                       int dedup, int* ids, float* dist, ihipStream_t* stream);
+// random-projection forest walk (predict/rp_forest.py): cand int32
+// [nq, width], per query the items of the leaves a best-first search
+// reaches until search_k ids are written, then -1
+int forest_queue();
+int forest_max_search();
+void forest_candidates_launch(const float* planes, const float* bias,
+                              const int* child, const int* roots,
+                              const int* leaf_off, const int* leaf_items,
+                              const float* Q, int* cand, long nq, int dim,
+                              int n_inner, int n_leaves, int T, long total,
+                              int search_k, long width, ihipStream_t* stream);
 
 }  // namespace lightctr

@@ -2,6 +2,7 @@ from .ann_index import ANNIndex
 from .forest import CompiledForest, LeafFeatures
 from .knn import FlatIndex, PQIndex
 from .predictor import BatchPredictor
+from .rp_forest import ForestIndex
 
 __all__ = ["ANNIndex", "BatchPredictor", "CompiledForest", "FlatIndex",
-           "LeafFeatures", "PQIndex"]
+           "ForestIndex", "LeafFeatures", "PQIndex"]
