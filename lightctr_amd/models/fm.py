@@ -9,11 +9,12 @@ Adagrad apply) — rebuilt GPU-first:
   * the train step is a handful of HIP kernel launches with no device->host
     syncs. Default backward_mode="segment": training forward (loss and
     per-entry (row, x) records fused in), radix sort with the records as
-    payload, a work-list pass and a per-piece segment reduce that recomputes
-    the gradients and applies the optimizer in place. "segment_emit" (the
-    same reduce fed by a per-entry gradient emit), "sorted" (walk into slabs
-    + bitmap compact + sparse optimizer) and "atomic" (scatter backward)
-    stay selectable
+    payload, and a tile-local segment reduce: every block finds the pieces
+    of its own tile of sorted entries, recomputes the gradients and applies
+    the optimizer in place. "segment_list" (the per-piece reduce fed by a
+    global work list), "segment_emit" (that reduce fed by a per-entry
+    gradient emit), "sorted" (walk into slabs + bitmap compact + sparse
+    optimizer) and "atomic" (scatter backward) stay selectable
   * CPU path uses the fp32 torch reference ops (same math; the test oracle)
   * optimizers: adagrad (reference default) and FTRL-proximal (BASELINE
     config #2: "FM k=16 ... FTRL fused update"); both are applied only to
@@ -81,7 +82,8 @@ class FMModel:
         self.uniq = torch.zeros(cap, dtype=torch.int32, device=self.device)
         self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._use_hip = self.device.type == "cuda"
-        # "segment" (default) | "segment_emit" | "sorted" | "atomic"
+        # "segment" (default) | "segment_list" | "segment_emit" | "sorted"
+        # | "atomic"
         # segment: sort, then one K-lane subgroup per piece (a run of equal
         # fids cut at multiples of segment_cap) sums its gradients and, for
         # a run that fits one piece, applies the optimizer in place; only
@@ -90,6 +92,11 @@ class FMModel:
         # The training forward writes one (row, x) record per entry, the
         # sort carries it as payload and the reduce recomputes each entry's
         # gradient from it: no per-entry gradient buffer, no loss kernel.
+        # A block owns a tile of sorted entries and finds its pieces itself
+        # (the tile is a multiple of segment_cap; a cap that does not divide
+        # it takes the list path).
+        # segment_list: the pieces come from a global work list (three
+        # library launches) and one subgroup walks each piece.
         # segment_emit: the same reduce fed by fm_backward_emit's per-entry
         # gradients through the sort permutation (the earlier pipeline,
         # kept for A/B).
@@ -132,10 +139,16 @@ class FMModel:
             ops = require_hip_ops()
             # fused_apply is a variant of the walk: asking for it selects
             # the sorted path
-            if self.backward_mode == "segment" and not self.fused_apply:
+            if (self.backward_mode in ("segment", "segment_list")
+                    and not self.fused_apply):
+                tiled = (self.backward_mode == "segment"
+                         and self._cap_tiles(ops))
+                # the work-list pass resets the spill counter; without it
+                # the forward does
                 loss, dpred, sumVX, rec = ops.fm_forward_train(
-                    row_ptr, fids, vals, self.W, self.V, labels, scale)
-                self._segment_backward(ops, fids, sumVX, dpred, rec)
+                    row_ptr, fids, vals, self.W, self.V, labels, scale,
+                    reset=self.count if tiled else None)
+                self._segment_backward(ops, fids, sumVX, dpred, rec, tiled)
                 return loss
             pred, sumVX = ops.fm_forward(row_ptr, fids, vals, self.W, self.V)
             loss, dpred = ops.logloss_grad(pred, labels, scale)
@@ -144,7 +157,8 @@ class FMModel:
                 self._segment_emit_backward(ops, row_ptr, fids, vals, sumVX,
                                             dpred)
                 return loss
-            if self.backward_mode in ("sorted", "segment", "segment_emit"):
+            if self.backward_mode in ("sorted", "segment", "segment_list",
+                                      "segment_emit"):
                 # contention-free backward: emit per-entry grads
                 # (coalesced), bit-range radix-sort the fids, then
                 # segment-reduce into the slabs with interior-store
@@ -238,14 +252,22 @@ class FMModel:
                                  self.nW, self.nV, self.gradW, self.gradV,
                                  self.h.lr, self.h.eps, self.h.l2)
 
-    def _segment_pieces(self, ops, sorted_fids):
-        """Work list + spill list + optimizer arguments shared by the two
-        segment modes."""
+    def _cap_tiles(self, ops) -> bool:
+        """The tile reduce needs whole pieces per tile: segment_cap must
+        divide the tile."""
+        tile, cap = ops.fm_segment_tile(), int(self.segment_cap)
+        return cap <= tile and tile % cap == 0
+
+    def _segment_pieces(self, ops, sorted_fids, worklist=True):
+        """Work list (unless the reduce finds its pieces itself) + spill
+        list + optimizer arguments shared by the segment modes."""
         nnz = sorted_fids.numel()
         cap = int(self.segment_cap)
-        # the work-list pass also resets the spill counter
-        piece_start, n_pieces = ops.segment_worklist(sorted_fids, cap,
-                                                     self.count)
+        if worklist:
+            # the work-list pass also resets the spill counter
+            lists = tuple(ops.segment_worklist(sorted_fids, cap, self.count))
+        else:
+            lists = (cap,)
         # a spilled run crosses a multiple of cap, and is a distinct fid
         spill = self.uniq[: min(self.uniq.numel(), nnz // cap + 1)]
         mode = self._opt_mode()
@@ -254,23 +276,27 @@ class FMModel:
         else:
             knobs = (self.h.ftrl_alpha, self.h.ftrl_beta, self.h.ftrl_l1,
                      self.h.ftrl_l2)
-        tail = (piece_start, n_pieces, self.gradW, self.gradV, spill,
+        tail = (*lists, self.gradW, self.gradV, spill,
                 self.count, self.W, self.V, self.nW, self.nV,
                 self.zW if mode != 1 else None,
                 self.zV if mode == 2 else None, mode, *knobs)
         kw = dict(v_lr=self.h.lr, v_eps=self.h.eps, v_l2=self.h.l2)
         return spill, tail, kw
 
-    def _segment_backward(self, ops, fids, sumVX, dpred, rec):
+    def _segment_backward(self, ops, fids, sumVX, dpred, rec, tiled):
         """Recompute reduce: the sort carries the forward's (row, x) records
-        and the reduce forms every entry's gradient itself."""
+        and the reduce forms every entry's gradient itself; tiled: without
+        a work list (backward_mode="segment"), else list-fed
+        ("segment_list")."""
         if fids.numel() == 0:
             return
         sorted_fids, sorted_rec = sort_ids_rec(fids, rec,
                                                self.h.num_features)
-        spill, tail, kw = self._segment_pieces(ops, sorted_fids)
-        ops.fm_segment_apply_rec(sorted_fids, sorted_rec, sumVX, dpred,
-                                 *tail, **kw)
+        spill, tail, kw = self._segment_pieces(ops, sorted_fids,
+                                               worklist=not tiled)
+        reduce = (ops.fm_segment_tile_rec if tiled
+                  else ops.fm_segment_apply_rec)
+        reduce(sorted_fids, sorted_rec, sumVX, dpred, *tail, **kw)
         self._sparse_apply(ops, spill)
 
     def _segment_emit_backward(self, ops, row_ptr, fids, vals, sumVX, dpred):

@@ -99,11 +99,14 @@ void check_cuda_rec(const at::Tensor& t, long n, const char* name) {
 
 // Training forward: fm_forward + logloss_grad in one launch, plus the
 // per-entry records rec[j] = {row of j, bits of vals[j]} that the segment
-// backward sorts by fid. Returns (loss, dpred, sumVX, rec).
+// backward sorts by fid. Returns (loss, dpred, sumVX, rec). `reset`
+// (optional int32 [1], the backward's spill counter) is zeroed by the same
+// launch.
 std::vector<at::Tensor> fm_forward_train(at::Tensor row_ptr, at::Tensor fids,
                                          at::Tensor vals, at::Tensor W,
                                          at::Tensor V, at::Tensor label,
-                                         double scale) {
+                                         double scale,
+                                         c10::optional<at::Tensor> reset) {
   check_cuda_i32(row_ptr, "row_ptr");
   check_cuda_i32(fids, "fids");
   check_cuda_f32(vals, "vals");
@@ -119,11 +122,19 @@ std::vector<at::Tensor> fm_forward_train(at::Tensor row_ptr, at::Tensor fids,
   auto dpred = at::empty({B}, W.options());
   auto sumVX = at::empty({B, K}, W.options());
   auto rec = at::empty({nnz, 2}, fids.options());
+  int* reset_ptr = nullptr;
+  if (reset.has_value()) {
+    check_cuda_i32(*reset, "reset");
+    CHK(reset->numel() >= 1, "reset must hold one int");
+    reset_ptr = reset->data_ptr<int>();
+    if (B <= 0) reset->zero_();  // nothing is launched for an empty batch
+  }
   lightctr::fm_forward_train_launch(
       row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
       W.data_ptr<float>(), V.data_ptr<float>(), label.data_ptr<float>(),
       (float)scale, loss.data_ptr<float>(), dpred.data_ptr<float>(),
-      sumVX.data_ptr<float>(), rec.data_ptr<int>(), B, K, cur_stream());
+      sumVX.data_ptr<float>(), rec.data_ptr<int>(), B, K, reset_ptr,
+      cur_stream());
   return {loss, dpred, sumVX, rec};
 }
 
@@ -286,20 +297,18 @@ std::vector<at::Tensor> segment_worklist(at::Tensor sorted_fids, int64_t cap,
   return {piece_start, n_pieces};
 }
 
-// Argument checks shared by the two entry sources of the segment backward
-void check_segment_common(const at::Tensor& sorted_fids,
-                          const at::Tensor& piece_start,
-                          const at::Tensor& n_pieces, const at::Tensor& gradW,
-                          const at::Tensor& gradV, const at::Tensor& spill,
-                          const at::Tensor& spill_count, const at::Tensor& W,
-                          const at::Tensor& V, const at::Tensor& nW,
-                          const at::Tensor& nV,
-                          const c10::optional<at::Tensor>& zW,
-                          const c10::optional<at::Tensor>& zV,
-                          int64_t opt_mode) {
+// Argument checks of every segment backward: slabs, spill list, parameters
+// and optimizer state
+void check_segment_state(const at::Tensor& sorted_fids,
+                         const at::Tensor& gradW, const at::Tensor& gradV,
+                         const at::Tensor& spill,
+                         const at::Tensor& spill_count, const at::Tensor& W,
+                         const at::Tensor& V, const at::Tensor& nW,
+                         const at::Tensor& nV,
+                         const c10::optional<at::Tensor>& zW,
+                         const c10::optional<at::Tensor>& zV,
+                         int64_t opt_mode) {
   check_cuda_i32(sorted_fids, "sorted_fids");
-  check_cuda_i32(piece_start, "piece_start");
-  check_cuda_i32(n_pieces, "n_pieces");
   check_cuda_i32(spill, "spill");
   check_cuda_i32(spill_count, "spill_count");
   check_cuda_f32(gradW, "gradW");
@@ -308,10 +317,8 @@ void check_segment_common(const at::Tensor& sorted_fids,
   check_cuda_f32(V, "V");
   check_cuda_f32(nW, "nW");
   check_cuda_f32(nV, "nV");
-  const long nnz = sorted_fids.numel();
   const int K = (int)V.size(1);
-  CHK(piece_start.numel() >= nnz, "piece_start must hold nnz entries");
-  CHK(n_pieces.numel() >= 1 && spill_count.numel() >= 1, "counters");
+  CHK(spill_count.numel() >= 1, "counters");
   CHK(gradV.numel() == V.numel() && gradW.numel() == W.numel() &&
           nV.numel() == V.numel() && nW.numel() == W.numel() &&
           V.numel() == W.numel() * K,
@@ -328,6 +335,26 @@ void check_segment_common(const at::Tensor& sorted_fids,
     check_cuda_f32(*zV, "zV");
     CHK(zV->numel() == V.numel(), "zV shape");
   }
+}
+
+// The same plus the work list of the two list-fed entry sources
+void check_segment_common(const at::Tensor& sorted_fids,
+                          const at::Tensor& piece_start,
+                          const at::Tensor& n_pieces, const at::Tensor& gradW,
+                          const at::Tensor& gradV, const at::Tensor& spill,
+                          const at::Tensor& spill_count, const at::Tensor& W,
+                          const at::Tensor& V, const at::Tensor& nW,
+                          const at::Tensor& nV,
+                          const c10::optional<at::Tensor>& zW,
+                          const c10::optional<at::Tensor>& zV,
+                          int64_t opt_mode) {
+  check_segment_state(sorted_fids, gradW, gradV, spill, spill_count, W, V, nW,
+                      nV, zW, zV, opt_mode);
+  check_cuda_i32(piece_start, "piece_start");
+  check_cuda_i32(n_pieces, "n_pieces");
+  CHK(piece_start.numel() >= sorted_fids.numel(),
+      "piece_start must hold nnz entries");
+  CHK(n_pieces.numel() >= 1, "counters");
 }
 
 // Segment backward: one K-lane subgroup per piece of the work list sums the
@@ -410,6 +437,45 @@ void fm_segment_apply_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
       zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
       (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
       num_cus, cur_stream());
+}
+
+// Tile-local segment backward from the sorted records: what
+// fm_segment_apply_rec computes, with every block finding the pieces of its
+// own tile of fm_segment_tile() entries (no work list). cap must divide the
+// tile. spill_count is not reset here: fm_forward_train(reset=) does that.
+void fm_segment_tile_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
+                         at::Tensor sumVX, at::Tensor dpred, int64_t cap,
+                         at::Tensor gradW, at::Tensor gradV, at::Tensor spill,
+                         at::Tensor spill_count, at::Tensor W, at::Tensor V,
+                         at::Tensor nW, at::Tensor nV,
+                         c10::optional<at::Tensor> zW,
+                         c10::optional<at::Tensor> zV, int64_t opt_mode,
+                         double p0, double p1, double p2, double p3,
+                         double v_lr, double v_eps, double v_l2) {
+  check_segment_state(sorted_fids, gradW, gradV, spill, spill_count, W, V, nW,
+                      nV, zW, zV, opt_mode);
+  const long tile = lightctr::fm_segment_tile();
+  CHK(cap >= 1 && (cap & (cap - 1)) == 0 && cap <= tile && tile % cap == 0,
+      "cap must be a power of two that divides the tile of ", tile);
+  const long nnz = sorted_fids.numel();
+  const int K = (int)V.size(1);
+  check_cuda_rec(sorted_rec, nnz, "sorted_rec");
+  check_cuda_f32(sumVX, "sumVX");
+  check_cuda_f32(dpred, "dpred");
+  const long B = dpred.numel();
+  CHK(sumVX.numel() == B * K, "sumVX must be [B, K]");
+  CHK(nnz == 0 || B >= 1, "entries need rows");
+  lightctr::fm_segment_tile_launch(
+      sorted_fids.data_ptr<int>(), sorted_rec.data_ptr<int>(),
+      sumVX.data_ptr<float>(), dpred.data_ptr<float>(), (int)B, (int)cap,
+      gradW.data_ptr<float>(), gradV.data_ptr<float>(),
+      spill.data_ptr<int>(), spill_count.data_ptr<int>(), (int)spill.numel(),
+      (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), W.data_ptr<float>(),
+      nW.data_ptr<float>(),
+      zW.has_value() ? zW->data_ptr<float>() : nullptr, nV.data_ptr<float>(),
+      zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
+      (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
+      cur_stream());
 }
 
 // ---- FFM ----
@@ -1673,7 +1739,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fm_forward_train", &fm_forward_train,
         "FM training forward -> (loss, dpred, sumVX, rec)",
         py::arg("row_ptr"), py::arg("fids"), py::arg("vals"), py::arg("W"),
-        py::arg("V"), py::arg("label"), py::arg("scale"));
+        py::arg("V"), py::arg("label"), py::arg("scale"),
+        py::arg("reset") = py::none());
   m.def("fm_backward", &fm_backward, "FM fused backward scatter");
   m.def("fm_backward_emit", &fm_backward_emit,
         "FM backward phase 1: per-entry grads (no atomics); pos=write slots",
@@ -1718,6 +1785,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("p0"), py::arg("p1"), py::arg("p2"), py::arg("p3"),
         py::arg("v_lr") = 0.05, py::arg("v_eps") = 1e-8,
         py::arg("v_l2") = 1e-5);
+  m.def("fm_segment_tile_rec", &fm_segment_tile_rec,
+        "tile-local segment reduce recomputing the gradients from sorted "
+        "records + fused optimizer; partial pieces spill",
+        py::arg("sorted_fids"), py::arg("sorted_rec"), py::arg("sumVX"),
+        py::arg("dpred"), py::arg("cap"), py::arg("gradW"), py::arg("gradV"),
+        py::arg("spill"), py::arg("spill_count"), py::arg("W"), py::arg("V"),
+        py::arg("nW"), py::arg("nV"), py::arg("zW"), py::arg("zV"),
+        py::arg("opt_mode"), py::arg("p0"), py::arg("p1"), py::arg("p2"),
+        py::arg("p3"), py::arg("v_lr") = 0.05, py::arg("v_eps") = 1e-8,
+        py::arg("v_l2") = 1e-5);
+  m.def("fm_segment_tile", &lightctr::fm_segment_tile,
+        "entries per block of fm_segment_tile_rec");
+  m.def("fm_segment_split", &lightctr::fm_segment_split,
+        "longest unit one subgroup sums in fm_segment_tile_rec");
   m.def("ffm_forward", &ffm_forward, "FFM pairwise forward (LDS-staged)");
   m.def("ffm_forward_pp", &ffm_forward_pp, "lane-per-pair FFM forward");
   m.def("ffm_row_emit", &ffm_row_emit,

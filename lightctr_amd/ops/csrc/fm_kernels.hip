@@ -215,9 +215,12 @@ __global__ void fm_forward_train_kernel(
     const float* __restrict__ vals, const float* __restrict__ W,
     const float* __restrict__ V, const float* __restrict__ label, float scale,
     float* __restrict__ loss, float* __restrict__ dpred,
-    float* __restrict__ sumVX, int2* __restrict__ rec, int B) {
+    float* __restrict__ sumVX, int2* __restrict__ rec, int B,
+    int* __restrict__ reset) {
   const int lane = threadIdx.x & (LCTR_WAVE - 1);
   const int row = blockIdx.x * (blockDim.x / LCTR_WAVE) + (threadIdx.x >> 6);
+  // the spill counter of the segment backward that follows in the stream
+  if (reset != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *reset = 0;
   if (row >= B) return;
   const float p = fm_forward_row<K, true>(row_ptr, fids, vals, W, V, sumVX,
                                           rec, row, lane);
@@ -915,6 +918,299 @@ __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Tile-local segment reduce (backward_mode="segment"): the reduce above
+// without its global work list. A block owns TILE consecutive sorted entries.
+// TILE is a multiple of CAP and pieces start at run heads and multiples of
+// CAP, so a tile holds whole pieces only and the block finds them itself:
+//   1. stage the tile's fids (plus the two neighbour fids, for the run
+//      head / tail tests) and records into LDS with coalesced loads;
+//   2. flag the unit starts and compact them with a block scan. A unit is a
+//      piece cut once more at the multiples of SPLIT of the sorted position
+//      (CUT = min(CAP, SPLIT)), so it is at most SPLIT long; a list entry
+//      also says whether its unit starts a piece;
+//   3. every K-lane subgroup takes NF units per turn and issues all their
+//      row loads (V, and for a one-unit piece nV/W/nW/zW, plus the first
+//      entry's sumVX/dpred) together: the fids and records come from LDS, so
+//      the only dependent global level left is the gathers themselves.
+//      A one-unit piece is finished on the spot as in the kernel above
+//      (whole: optimizer in place; partial: slabs + spill list), with the
+//      same per-entry expressions in the same order. A unit of a longer
+//      piece leaves its partial (acc[k], accw) in its own LDS slot, so the
+//      units of a long piece are spread over the block's subgroups;
+//   4. after a block barrier one subgroup per multi-unit piece adds the
+//      piece's partials in ascending position order (no float atomics in
+//      LDS: a whole piece's sum does not depend on scheduling) and finishes
+//      the piece the same way.
+// No parameter store of a fid precedes a read of its old V: one-unit whole
+// pieces own their fid alone, multi-unit pieces store only after the
+// barrier, partial pieces never store (the spill apply, launched next, does).
+// Slots: a unit of a multi-unit piece either starts on a multiple of CUT
+// (slot 2c for cell c) or is its piece's first unit and reaches the end of
+// its cell (slot 2c + 1, at most one per cell): 2 * TILE / SPLIT slots.
+// ---------------------------------------------------------------------------
+constexpr int kFmTilePieceBit = 1 << 30;  // list entry: unit starts a piece
+
+template <int K, int TILE, int SPLIT, int NF>
+__global__ __launch_bounds__(256) void fm_segment_tile_kernel(
+    const int* __restrict__ sorted_fids, const int2* __restrict__ rec,
+    const float* __restrict__ sumVX, const float* __restrict__ dpred, int B,
+    int cap, float* __restrict__ gradW, float* __restrict__ gradV,
+    int* __restrict__ spill, int* __restrict__ spill_count, int spill_cap,
+    int nnz, int opt_mode, float* __restrict__ V, FmOptArgs oa) {
+  constexpr int NT = 256;
+  constexpr int NW = NT / LCTR_WAVE;
+  constexpr int ITEMS = TILE / NT;
+  constexpr int NSG = NT / K;  // subgroups per block
+  constexpr int D = 4;         // gathers in flight per lane inside a unit
+  constexpr int NSLOT = 2 * TILE / SPLIT;
+  static_assert(TILE % NT == 0 && TILE % SPLIT == 0, "tile shape");
+
+  __shared__ int s_fid[TILE + 2];  // [0] = fid before the tile, [n+1] after
+  __shared__ int2 s_rec[TILE];
+  __shared__ int s_unit[TILE + 1];
+  __shared__ int s_multi[TILE / SPLIT];
+  __shared__ float s_part[NSLOT * (K + 1)];
+  __shared__ int s_wave_tot[NW];
+  __shared__ int s_nmulti;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (LCTR_WAVE - 1);
+  const int wv = tid >> 6;
+  const int sg = tid / K;
+  const int k = tid % K;
+  const long t0 = (long)blockIdx.x * TILE;
+  const int n = (int)min((long)TILE, (long)nnz - t0);
+  if (n <= 0) return;
+  const int cut = min(cap, SPLIT);
+
+  // -- 1. stage ------------------------------------------------------------
+#pragma unroll
+  for (int u = 0; u < ITEMS; ++u) {
+    const int i = u * NT + tid;
+    if (i < n) {
+      s_fid[i + 1] = sorted_fids[t0 + i];
+      s_rec[i] = rec[t0 + i];
+    }
+  }
+  if (tid == 0) {
+    s_fid[0] = (t0 > 0) ? sorted_fids[t0 - 1] : 0;
+    s_fid[n + 1] = (t0 + n < nnz) ? sorted_fids[t0 + n] : 0;
+    s_nmulti = 0;
+  }
+  __syncthreads();
+  // run head at local i / run tail before local i (neighbours guarded)
+  auto is_head = [&](int i) {
+    return (t0 + i == 0) || (s_fid[i] != s_fid[i + 1]);
+  };
+  auto is_tail_before = [&](int i, int fid) {
+    return (t0 + i >= nnz) || (s_fid[i + 1] != fid);
+  };
+
+  // -- 2. local unit list --------------------------------------------------
+  int mine[ITEMS];
+  int cnt = 0;
+#pragma unroll
+  for (int u = 0; u < ITEMS; ++u) {
+    const int i = tid * ITEMS + u;
+    mine[u] = -1;
+    if (i < n) {
+      const long gi = t0 + i;
+      const bool head = is_head(i);
+      if (head || (gi & (cut - 1)) == 0) {
+        const bool pstart = head || (gi & (cap - 1)) == 0;
+        mine[u] = i | (pstart ? kFmTilePieceBit : 0);
+        ++cnt;
+      }
+    }
+  }
+  int scan = cnt;
+#pragma unroll
+  for (int s = 1; s < LCTR_WAVE; s <<= 1) {
+    const int t = __shfl_up(scan, s);
+    if (lane >= s) scan += t;
+  }
+  if (lane == LCTR_WAVE - 1) s_wave_tot[wv] = scan;
+  __syncthreads();
+  int pos = scan - cnt, nu = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    const int t = s_wave_tot[w];
+    if (w < wv) pos += t;
+    nu += t;
+  }
+#pragma unroll
+  for (int u = 0; u < ITEMS; ++u)
+    if (mine[u] >= 0) s_unit[pos++] = mine[u];
+  if (tid == 0) s_unit[nu] = n | kFmTilePieceBit;  // end of the last unit
+  __syncthreads();
+
+  // what a finished piece does with its sum: `whole` applies the optimizer
+  // to the rows loaded before the sum, otherwise the sum goes to the slabs
+  // and the run's head piece reports the fid
+  auto append_spill = [&](bool spill_me, int fid) {
+    const unsigned long long m = __ballot(spill_me);
+    if (m) {
+      int slot = 0;
+      if (lane == 0) slot = atomicAdd(spill_count, __popcll(m));
+      slot = __shfl(slot, 0) + __popcll(m & ((1ull << lane) - 1ull));
+      if (spill_me && slot < spill_cap) spill[slot] = fid;  // clamp
+    }
+  };
+  auto gather = [&](int i, float& sv, float& d) {
+    // rows come from the forward kernel; the clamp only keeps a foreign
+    // record buffer from reading outside sumVX / dpred
+    const int row = min(max(s_rec[i].x, 0), B - 1);
+    sv = sumVX[(size_t)row * K + k];
+    d = dpred[row];
+  };
+  auto add = [&](int i, float sv, float d, float v, float& acc,
+                 float& accw) {
+    const float x = __int_as_float(s_rec[i].y);
+    acc += d * (sv - v * x) * x;
+    accw += d * x;
+  };
+
+  // -- 3. units ------------------------------------------------------------
+  for (int j0 = 0; j0 < nu; j0 += NSG * NF) {
+    int us[NF], ue[NF], fid[NF];
+    bool single[NF], first[NF], whole[NF], headp[NF];
+    float v[NF], nv[NF], z[NF], w[NF], nw[NF], zw[NF], sv0[NF], d0[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      const int j = j0 + f * NSG + sg;
+      us[f] = ue[f] = 0;
+      fid[f] = 0;
+      single[f] = first[f] = whole[f] = headp[f] = false;
+      v[f] = nv[f] = z[f] = w[f] = nw[f] = zw[f] = sv0[f] = d0[f] = 0.f;
+      if (j < nu) {
+        const int a = s_unit[j], b = s_unit[j + 1];
+        us[f] = a & (kFmTilePieceBit - 1);
+        ue[f] = b & (kFmTilePieceBit - 1);
+        first[f] = (a & kFmTilePieceBit) != 0;
+        single[f] = first[f] && (b & kFmTilePieceBit) != 0;
+        fid[f] = s_fid[us[f] + 1];
+        const size_t off = (size_t)fid[f] * K + k;
+        v[f] = V[off];
+        gather(us[f], sv0[f], d0[f]);
+        if (single[f]) {
+          headp[f] = is_head(us[f]);
+          whole[f] = headp[f] && is_tail_before(ue[f], fid[f]);
+        }
+        if (whole[f]) {
+          nv[f] = oa.nV[off];
+          if (opt_mode == 2) z[f] = oa.zV[off];
+          if (k == 0) {
+            w[f] = oa.W[fid[f]];
+            nw[f] = oa.nW[fid[f]];
+            if (opt_mode != 1) zw[f] = oa.zW[fid[f]];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      bool spill_me = false;
+      if (ue[f] > us[f]) {
+        float acc = 0.f, accw = 0.f;
+        for (int e = us[f] + 1; e < ue[f]; e += D) {
+          float sv[D], d[D];
+#pragma unroll
+          for (int u = 0; u < D; ++u) {
+            sv[u] = d[u] = 0.f;
+            if (e + u < ue[f]) gather(e + u, sv[u], d[u]);
+          }
+#pragma unroll
+          for (int u = 0; u < D; ++u)
+            if (e + u < ue[f]) add(e + u, sv[u], d[u], v[f], acc, accw);
+        }
+        // the head entry last, as in fm_segment_apply_kernel
+        add(us[f], sv0[f], d0[f], v[f], acc, accw);
+        const size_t off = (size_t)fid[f] * K + k;
+        if (whole[f]) {
+          fm_opt_step_v(opt_mode, v[f], nv[f], z[f], acc, oa);
+          if (opt_mode == 2) oa.zV[off] = z[f];
+          oa.nV[off] = nv[f];
+          V[off] = v[f];
+          if (k == 0) {
+            fm_opt_step_w(opt_mode, w[f], nw[f], zw[f], accw, oa);
+            if (opt_mode != 1) oa.zW[fid[f]] = zw[f];
+            oa.nW[fid[f]] = nw[f];
+            oa.W[fid[f]] = w[f];
+          }
+        } else if (single[f]) {
+          atomicAdd(&gradV[off], acc);
+          if (k == 0) atomicAdd(&gradW[fid[f]], accw);
+          spill_me = headp[f] && (k == 0);
+        } else {
+          const int c = us[f] / SPLIT;
+          const int slot = 2 * c + ((us[f] & (SPLIT - 1)) ? 1 : 0);
+          s_part[slot * (K + 1) + k] = acc;
+          if (k == 0) {
+            s_part[slot * (K + 1) + K] = accw;
+            if (first[f]) s_multi[atomicAdd(&s_nmulti, 1)] = j0 + f * NSG + sg;
+          }
+        }
+      }
+      append_spill(spill_me, fid[f]);
+    }
+  }
+  __syncthreads();
+
+  // -- 4. multi-unit pieces ------------------------------------------------
+  const int nm = s_nmulti;
+  for (int m0 = 0; m0 < nm; m0 += NSG) {
+    bool spill_me = false;
+    int fidm = 0;
+    if (m0 + sg < nm) {
+      int j = s_multi[m0 + sg];
+      const int ps = s_unit[j] & (kFmTilePieceBit - 1);
+      fidm = s_fid[ps + 1];
+      const size_t off = (size_t)fidm * K + k;
+      // the piece's end: the next list entry that starts a piece
+      int j1 = j + 1;
+      while (!(s_unit[j1] & kFmTilePieceBit)) ++j1;
+      const int pe = s_unit[j1] & (kFmTilePieceBit - 1);
+      const bool whole = is_head(ps) && is_tail_before(pe, fidm);
+      float v = 0.f, nv = 0.f, z = 0.f, w = 0.f, nw = 0.f, zw = 0.f;
+      if (whole) {
+        v = V[off];
+        nv = oa.nV[off];
+        if (opt_mode == 2) z = oa.zV[off];
+        if (k == 0) {
+          w = oa.W[fidm];
+          nw = oa.nW[fidm];
+          if (opt_mode != 1) zw = oa.zW[fidm];
+        }
+      }
+      float acc = 0.f, accw = 0.f;
+      for (; j < j1; ++j) {
+        const int s = s_unit[j] & (kFmTilePieceBit - 1);
+        const int slot = 2 * (s / SPLIT) + ((s & (SPLIT - 1)) ? 1 : 0);
+        acc += s_part[slot * (K + 1) + k];
+        accw += s_part[slot * (K + 1) + K];
+      }
+      if (whole) {
+        fm_opt_step_v(opt_mode, v, nv, z, acc, oa);
+        if (opt_mode == 2) oa.zV[off] = z;
+        oa.nV[off] = nv;
+        V[off] = v;
+        if (k == 0) {
+          fm_opt_step_w(opt_mode, w, nw, zw, accw, oa);
+          if (opt_mode != 1) oa.zW[fidm] = zw;
+          oa.nW[fidm] = nw;
+          oa.W[fidm] = w;
+        }
+      } else {
+        atomicAdd(&gradV[off], acc);
+        if (k == 0) atomicAdd(&gradW[fidm], accw);
+        spill_me = is_head(ps) && (k == 0);
+      }
+    }
+    append_spill(spill_me, fidm);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Bitmap -> unique-fid list compaction. One thread per 64-feature word;
 // clears the word as it goes so the bitmap is reusable next step.
 // ---------------------------------------------------------------------------
@@ -1041,14 +1337,15 @@ void fm_forward_train_launch(const int* row_ptr, const int* fids,
                              const float* vals, const float* W, const float* V,
                              const float* label, float scale, float* loss,
                              float* dpred, float* sumVX, int* rec, int B,
-                             int K, hipStream_t stream) {
+                             int K, int* reset, hipStream_t stream) {
   if (B <= 0) return;
   const int wpb = waves_per_block();
   dim3 block(wpb * LCTR_WAVE);
   dim3 grid((B + wpb - 1) / wpb);
   DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_train_kernel<KC>), grid, block,
                                    0, stream, row_ptr, fids, vals, W, V, label,
-                                   scale, loss, dpred, sumVX, (int2*)rec, B));
+                                   scale, loss, dpred, sumVX, (int2*)rec, B,
+                                   reset));
 }
 
 void logloss_grad_launch(const float* pred, const float* label, float* loss,
@@ -1267,6 +1564,63 @@ void fm_segment_recompute_launch(
   const FmSrcRecompute src{(const int2*)rec, sumVX, dpred, B};
   DISPATCH_K(K, (fm_segment_launch_one<KC, FmSrcRecompute, kFmRecomputeDepth>(
                     a, src, stream)));
+}
+
+// Shape of the tile reduce: entries per block, longest unit, units a
+// subgroup keeps in flight. Swept over {256, 512, 1024} x {16, 32, 64} x
+// {1, 2, 4} at the flagship shape (profiles/r5_01_fm_tile.txt): the smallest
+// tile wins (more blocks for the dispatcher to balance, 8 blocks per CU),
+// SPLIT 16 and 32 tie, and a second unit in flight buys nothing at TILE 256
+// (four in flight lose 5 %): occupancy beats lookahead here too.
+constexpr int kFmTile = 256;
+constexpr int kFmTileSplit = 32;
+constexpr int kFmTileFlight = 1;
+
+struct FmTileArgs {
+  const int* sorted_fids;
+  const int* rec;
+  const float* sumVX;
+  const float* dpred;
+  int B, cap;
+  float* gradW;
+  float* gradV;
+  int* spill;
+  int* spill_count;
+  int spill_cap, nnz, opt_mode;
+  float* V;
+  FmOptArgs oa;
+};
+
+template <int K, int TILE, int SPLIT, int NF>
+static void fm_segment_tile_launch_one(const FmTileArgs& a,
+                                       hipStream_t stream) {
+  // one block per tile: the count is known here, the dispatcher balances
+  const int blocks = (int)(((long)a.nnz + TILE - 1) / TILE);
+  hipLaunchKernelGGL((fm_segment_tile_kernel<K, TILE, SPLIT, NF>),
+                     dim3(blocks), dim3(256), 0, stream, a.sorted_fids,
+                     (const int2*)a.rec, a.sumVX, a.dpred, a.B, a.cap, a.gradW,
+                     a.gradV, a.spill, a.spill_count, a.spill_cap, a.nnz,
+                     a.opt_mode, a.V, a.oa);
+}
+
+int fm_segment_tile() { return kFmTile; }
+int fm_segment_split() { return kFmTileSplit; }
+
+void fm_segment_tile_launch(const int* sorted_fids, const int* rec,
+                            const float* sumVX, const float* dpred, int B,
+                            int cap, float* gradW, float* gradV, int* spill,
+                            int* spill_count, int spill_cap, int nnz, int K,
+                            int opt_mode, float* V, float* W, float* nW,
+                            float* zW, float* nV, float* zV, float p0,
+                            float p1, float p2, float p3, float q0, float q1,
+                            float q2, hipStream_t stream) {
+  if (nnz <= 0 || B <= 0) return;
+  const FmTileArgs a{sorted_fids, rec, sumVX, dpred, B, cap, gradW, gradV,
+                     spill, spill_count, spill_cap, nnz, opt_mode, V,
+                     FmOptArgs{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1,
+                               q2}};
+  DISPATCH_K(K, (fm_segment_tile_launch_one<KC, kFmTile, kFmTileSplit,
+                                            kFmTileFlight>(a, stream)));
 }
 
 void bitmap_compact_launch(unsigned long long* bitmap, int nwords,

@@ -46,7 +46,7 @@ void fm_forward_train_launch(const int* row_ptr, const int* fids,
                              const float* vals, const float* W, const float* V,
                              const float* label, float scale, float* loss,
                              float* dpred, float* sumVX, int* rec, int B,
-                             int K, ihipStream_t* stream);
+                             int K, int* reset, ihipStream_t* stream);
 void fm_segment_recompute_launch(
     const int* sorted_fids, const int* rec, const float* sumVX,
     const float* dpred, int B, const int* piece_start, const int* n_pieces,
@@ -54,6 +54,18 @@ void fm_segment_recompute_launch(
     int nnz, int K, int opt_mode, float* V, float* W, float* nW, float* zW,
     float* nV, float* zV, float p0, float p1, float p2, float p3, float q0,
     float q1, float q2, int num_cus, ihipStream_t* stream);
+// tile-local segment reduce: needs cap <= fm_segment_tile() and the tile a
+// multiple of cap; no work list
+int fm_segment_tile();
+int fm_segment_split();
+void fm_segment_tile_launch(const int* sorted_fids, const int* rec,
+                            const float* sumVX, const float* dpred, int B,
+                            int cap, float* gradW, float* gradV, int* spill,
+                            int* spill_count, int spill_cap, int nnz, int K,
+                            int opt_mode, float* V, float* W, float* nW,
+                            float* zW, float* nV, float* zV, float p0,
+                            float p1, float p2, float p3, float q0, float q1,
+                            float q2, ihipStream_t* stream);
 void bitmap_compact_launch(unsigned long long* bitmap, int nwords,
                            int* out_fids, int* out_count, int cap,
                            ihipStream_t* stream);
