@@ -112,6 +112,13 @@ class FMModel:
         # profiles/r2_06_fm_step_fused_ab.txt). Two-phase stays default;
         # kept selectable + parity tested.
         self.fused_apply = False
+        # record sort of the segment modes: "onesweep" (the single-purpose
+        # sort of sort_kernels.hip) | "rocprim"; same permutation either way.
+        # sort_status is the word a bounded look-back spin of the onesweep
+        # sort marks on give-up; it stays 0 in a healthy run.
+        self.sort_impl = "onesweep"
+        self.sort_status = torch.zeros(1, dtype=torch.int32,
+                                       device=self.device)
         if self._use_hip:
             require_hip_ops()  # fail loudly if extension missing on GPU
 
@@ -290,8 +297,9 @@ class FMModel:
         ("segment_list")."""
         if fids.numel() == 0:
             return
-        sorted_fids, sorted_rec = sort_ids_rec(fids, rec,
-                                               self.h.num_features)
+        sorted_fids, sorted_rec = sort_ids_rec(
+            fids, rec, self.h.num_features, impl=self.sort_impl,
+            status=self.sort_status)
         spill, tail, kw = self._segment_pieces(ops, sorted_fids,
                                                worklist=not tiled)
         reduce = (ops.fm_segment_tile_rec if tiled

@@ -54,8 +54,20 @@ def sort_ids(fids, upper: int):
     return require_hip_ops().radix_sort_index(fids, end_bit)
 
 
-def sort_ids_rec(fids, rec, upper: int):
+def sort_ids_rec(fids, rec, upper: int, impl: str = "onesweep", status=None):
     """(sorted, sorted_rec): the same bit-range sort carrying one 8-byte
-    record per id (rec int32 [n, 2]) as its payload instead of an index."""
+    record per id (rec int32 [n, 2]) as its payload instead of an index.
+
+    impl="onesweep": the single-purpose sort (one memset, one histogram
+    kernel, one scatter kernel per 8-bit pass); status is the caller's int32
+    word that a bounded look-back spin marks on give-up. impl="rocprim":
+    rocPRIM's radix sort, also taken where the onesweep binding does not
+    accept the arguments (end_bit 32, n >= 2^30). Both give the same stable
+    permutation."""
+    if impl not in ("onesweep", "rocprim"):
+        raise ValueError(f"unknown sort impl {impl!r}")
+    ops = require_hip_ops()
     end_bit = max(1, int(upper - 1).bit_length())
-    return require_hip_ops().radix_sort_rec(fids, rec, end_bit)
+    if impl == "onesweep" and end_bit <= 31 and fids.numel() < (1 << 30):
+        return ops.onesweep_sort_rec(fids, rec, end_bit, status)
+    return ops.radix_sort_rec(fids, rec, end_bit)

@@ -1204,6 +1204,44 @@ std::vector<at::Tensor> radix_sort_rec(at::Tensor keys, at::Tensor rec,
   return {sorted, sorted_rec};
 }
 
+// The same result from the single-purpose onesweep sort (sort_kernels.hip):
+// five launches for three passes. status: int32 [1] owned by the caller; the
+// sort ORs a nonzero code into it if a look-back spin gives up and never
+// zeroes it.
+std::vector<at::Tensor> onesweep_sort_rec(at::Tensor keys, at::Tensor rec,
+                                          int64_t end_bit,
+                                          c10::optional<at::Tensor> status) {
+  check_cuda_i32(keys, "keys");
+  CHK(end_bit >= 1 && end_bit <= 31, "end_bit in [1,31]");
+  CHK(keys.numel() < (1L << 30), "n must be below 2^30");
+  const int n = (int)keys.numel();
+  check_cuda_rec(rec, n, "rec");
+  if (status.has_value()) {
+    check_cuda_i32(*status, "status");
+    CHK(status->numel() >= 1, "status must hold one word");
+  }
+  auto sorted = at::empty_like(keys);
+  auto sorted_rec = at::empty_like(rec);
+  if (n == 0) return {sorted, sorted_rec};
+  auto st = status.has_value() ? *status : at::zeros({1}, keys.options());
+  const unsigned long bytes =
+      lightctr::onesweep_sort_work_bytes(n, (int)end_bit);
+  auto work = at::empty({(long)bytes}, keys.options().dtype(at::kByte));
+  at::Tensor keys_tmp, rec_tmp;
+  if (end_bit > 8) {
+    keys_tmp = at::empty_like(keys);
+    rec_tmp = at::empty_like(rec);
+  }
+  lightctr::onesweep_sort_rec_launch(
+      work.data_ptr(), keys.data_ptr<int>(), sorted.data_ptr<int>(),
+      end_bit > 8 ? keys_tmp.data_ptr<int>() : nullptr, rec.data_ptr<int>(),
+      sorted_rec.data_ptr<int>(),
+      end_bit > 8 ? rec_tmp.data_ptr<int>() : nullptr, n, (int)end_bit,
+      st.data_ptr<int>(), cur_stream());
+  return {sorted, sorted_rec};
+}
+
+
 at::Tensor colsum(at::Tensor dZ) {
   check_cuda_f32(dZ, "dZ");
   const int M = (int)dZ.size(0), N = (int)dZ.size(1);
@@ -1878,6 +1916,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bit-range radix sort with [n,2] int32 records as payload -> "
         "(sorted, sorted_rec)",
         py::arg("keys"), py::arg("rec"), py::arg("end_bit"));
+  m.def("onesweep_sort_rec", &onesweep_sort_rec,
+        "single-purpose onesweep sort with [n,2] int32 records as payload "
+        "-> (sorted, sorted_rec); same result as radix_sort_rec",
+        py::arg("keys"), py::arg("rec"), py::arg("end_bit"),
+        py::arg("status") = py::none());
+  m.def("onesweep_sort_tile", &lightctr::onesweep_sort_tile,
+        "entries per tile of onesweep_sort_rec");
   m.def("colsum", &colsum, "bias gradient column sum");
   m.def("to_bf16", &to_bf16, "f32 -> bf16 convert");
   m.def("dense_adam", &dense_adam, "dense Adam + bf16 mirror refresh");

@@ -337,6 +337,17 @@ void radix_sort_pairs_rec_launch(void* temp, unsigned long temp_bytes,
                                  const int* keys_in, int* keys_out,
                                  const int* rec_in, int* rec_out, int n,
                                  int end_bit, ihipStream_t* stream);
+// single-purpose onesweep sort of (key, 8-byte record): one memset, one
+// histogram kernel, one scatter kernel per 8-bit pass. 1 <= end_bit <= 31,
+// n < 2^30. work: onesweep_sort_work_bytes() bytes; keys_tmp / rec_tmp: n
+// entries each, used from two passes on; status: caller-owned word, a
+// nonzero code is ORed in if a look-back spin gives up (never zeroed here)
+int onesweep_sort_tile();
+unsigned long onesweep_sort_work_bytes(int n, int end_bit);
+void onesweep_sort_rec_launch(void* work, const int* keys_in, int* keys_out,
+                              int* keys_tmp, const int* rec_in, int* rec_out,
+                              int* rec_tmp, int n, int end_bit, int* status,
+                              ihipStream_t* stream);
 // work list of the segment backward: compacted piece starts of a sorted
 // stream + their count (device side); zero_me (optional) is reset to 0
 unsigned long segment_worklist_temp_bytes(int n);

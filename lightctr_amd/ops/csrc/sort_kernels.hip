@@ -14,6 +14,8 @@
 // indices move through the 2-3 radix passes. Host-side wrappers live
 // here because rocPRIM instantiates device kernels (must be compiled by
 // hipcc); tensor plumbing stays in bindings.cpp.
+#include <algorithm>
+
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -82,6 +84,385 @@ void radix_sort_pairs_rec_launch(void* temp, size_t temp_bytes,
   LCTR_CHECK_HIP(rocprim::radix_sort_pairs(
       temp, temp_bytes, keys_in, keys_out, (const SortRec*)rec_in,
       (SortRec*)rec_out, (size_t)n, 0u, (unsigned)end_bit, stream, false));
+}
+
+// ---------------------------------------------------------------------------
+// Single-purpose onesweep sort for the (fid, record) stream.
+//
+// Stable LSD radix sort, 8 bits per pass, of int32 keys in [0, 2^end_bit)
+// with an 8-byte record payload: one memset, one histogram kernel and one
+// scatter kernel per pass (rocPRIM's onesweep at this size: seven fills, a
+// histogram, a scan and three passes).
+//
+// Control block (zeroed by the one memset, at the start of the work
+// allocation, a multiple of 16 bytes): kOsMaxPasses x 256 digit counters and
+// one ticket counter per pass. Behind it, one look-back state array per pass,
+// [tiles][256] words, zeroed by the histogram kernel: a scatter kernel polls
+// them, and it starts only after the histogram kernel has ended.
+//
+// Histogram: every block counts all digit places of its keys in LDS and
+// flushes one global atomic per non-empty bin. The exclusive scan of a place
+// is done by that pass's tile 0 (the block holding ticket 0), which folds the
+// digit bases into the inclusive prefix it publishes; every later tile gets
+// them through the look-back chain and never reads the histogram.
+//
+// Scatter pass (decoupled look-back):
+//   * the tile id is a ticket (one atomicAdd, broadcast through LDS), so a
+//     tile only waits on tiles whose blocks have already started: no
+//     co-residency needed, grid = number of tiles;
+//   * a state is one word {2-bit status | 30-bit count} per (tile, digit),
+//     stored and polled with relaxed agent-scope atomics (the data is the
+//     flag; no fence on the path). The aggregate is published as soon as the
+//     tile's digit counts are known, the inclusive prefix as soon as the
+//     look-back ends, before the scatter;
+//   * every spin is bounded: on give-up the block ORs a code into `status`
+//     (caller-owned, never zeroed here) and returns;
+//   * ranking is wave-level digit matching (a per-wave table of 64-bit lane
+//     masks in LDS) with per-wave digit counters in LDS; a wave owns a
+//     contiguous chunk of the tile and walks it in 64-entry rows, so ties stay
+//     in input order;
+//   * keys and records are reordered by digit in LDS and written out with
+//     consecutive lanes on consecutive addresses. The reorder buffers reuse
+//     the ranking tables' bytes: 50 KB per 4096-entry tile, 3 blocks per CU,
+//     so the flagship's 624 tiles are resident at once.
+// ---------------------------------------------------------------------------
+constexpr int kOsRadix = 256;
+constexpr int kOsMaxPasses = 4;
+constexpr int kOsCtrlWords = kOsMaxPasses * kOsRadix + kOsMaxPasses;
+static_assert(kOsCtrlWords * 4 % 16 == 0, "memset block is 16-byte padded");
+constexpr unsigned kOsCountMask = 0x3fffffffu;
+constexpr unsigned kOsAggregate = 1u << 30;
+constexpr unsigned kOsPrefix = 2u << 30;
+constexpr unsigned kOsSpinLimit = 1u << 20;
+constexpr int kOsHistMaxThreads = 1024;
+constexpr int kOsHistMaxBlocks = 256;
+// tile shape and look-back window: the winners of the sweep in
+// profiles/r6_01_fm_sort.txt (tiles of 2048 / 4096 / 8192 entries, 256- and
+// 512-thread blocks, windows of 1..64); only this shape is built
+constexpr int kOsThreads = 512;
+constexpr int kOsItems = 8;
+constexpr int kOsWindow = 4;
+
+#define OS_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+__global__ __launch_bounds__(kOsHistMaxThreads) void onesweep_hist_kernel(
+    const int* __restrict__ keys, int n, int passes, unsigned keymask,
+    unsigned* ghist, uint4* state, long state_vec4) {
+  __shared__ unsigned h[kOsMaxPasses * kOsRadix];
+  const int tid = threadIdx.x, threads = blockDim.x;
+  for (int i = tid; i < passes * kOsRadix; i += threads) h[i] = 0;
+  const long gstride = (long)gridDim.x * threads;
+  for (long i = (long)blockIdx.x * threads + tid; i < state_vec4; i += gstride)
+    state[i] = make_uint4(0u, 0u, 0u, 0u);
+  __syncthreads();
+  const int stride = (int)gstride;
+#pragma unroll 4
+  for (int i = blockIdx.x * threads + tid; i < n; i += stride) {
+    const unsigned k = (unsigned)keys[i] & keymask;
+#pragma unroll
+    for (int p = 0; p < kOsMaxPasses; ++p)
+      if (p < passes) atomicAdd(&h[p * kOsRadix + ((k >> (8 * p)) & 255u)], 1u);
+  }
+  __syncthreads();
+  for (int i = tid; i < passes * kOsRadix; i += threads) {
+    const unsigned c = h[i];
+    if (c) atomicAdd(&ghist[i], c);
+  }
+}
+
+// exclusive scan of one value per thread over threads 0..255 (threads past
+// 255 pass 0 and ignore the result); wsum: 4 words of LDS, one use per array
+__device__ __forceinline__ unsigned os_scan256(unsigned v, unsigned* wsum,
+                                               int tid) {
+  const int lane = tid & 63, w = tid >> 6;
+  unsigned incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(incl, o);
+    if (lane >= o) incl += t;
+  }
+  if (tid < kOsRadix && lane == 63) wsum[w] = incl;
+  __syncthreads();
+  unsigned add = 0;
+  if (tid < kOsRadix)
+    for (int k = 0; k < w; ++k) add += wsum[k];
+  return incl - v + add;
+}
+
+// LDS of a scatter block: the reorder buffers (8 + 4 bytes per entry), which
+// take over the space of the ranking phase's per-wave digit masks and counters
+// and the tile's digit bases, then the per-digit output offsets and a few
+// words of scan and hand-over scratch.
+template <int THREADS, int IPT>
+constexpr int os_smem_bytes() {
+  constexpr int rank_bytes = (THREADS / 64) * kOsRadix * 12 + kOsRadix * 4;
+  constexpr int tile_bytes = THREADS * IPT * 12;
+  return (tile_bytes > rank_bytes ? tile_bytes : rank_bytes) + kOsRadix * 4 +
+         48;
+}
+
+template <int THREADS, int IPT>
+__global__ __launch_bounds__(THREADS) void onesweep_scatter_kernel(
+    const int* __restrict__ keys_in,
+    const unsigned long long* __restrict__ rec_in, int* __restrict__ keys_out,
+    unsigned long long* __restrict__ rec_out, int n, int shift,
+    unsigned keymask, const unsigned* __restrict__ ghist, unsigned* ticket,
+    unsigned* state, int* status) {
+  constexpr int TILE = THREADS * IPT, NW = THREADS / 64;
+  static_assert(THREADS >= kOsRadix && THREADS % 64 == 0, "one thread/digit");
+  constexpr int rank_bytes = NW * kOsRadix * 12 + kOsRadix * 4;
+  constexpr int main_bytes = TILE * 12 > rank_bytes ? TILE * 12 : rank_bytes;
+  extern __shared__ __attribute__((aligned(16))) unsigned char os_smem[];
+  // reorder phase
+  unsigned long long* lrec = (unsigned long long*)os_smem;  // [TILE]
+  unsigned* lkeys = (unsigned*)(os_smem + TILE * 8);        // [TILE]
+  // ranking phase, same bytes
+  unsigned long long* wmask = (unsigned long long*)os_smem;   // [NW][256]
+  unsigned* wcnt = (unsigned*)(os_smem + NW * kOsRadix * 8);  // [NW][256]
+  unsigned* lbase = wcnt + NW * kOsRadix;                     // [256]
+  // both phases
+  int* off = (int*)(os_smem + main_bytes);         // [256]
+  unsigned* wsum_a = (unsigned*)(off + kOsRadix);  // [4]
+  unsigned* wsum_b = wsum_a + 4;                   // [4]
+  unsigned* misc = wsum_b + 4;                     // ticket, give-up
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (tid == 0) {
+    misc[0] = atomicAdd(ticket, 1u);
+    misc[1] = 0;
+  }
+  // masks and counters are contiguous: NW * 256 * 3 words
+  for (int i = tid; i < NW * kOsRadix * 3; i += THREADS)
+    ((unsigned*)os_smem)[i] = 0;
+  __syncthreads();
+  const int tile = (int)misc[0];
+  const int tile_base = tile * TILE;
+  const int valid_n = min(TILE, n - tile_base);
+
+  // a wave owns entries [w * IPT * 64, (w + 1) * IPT * 64) of the tile and
+  // reads them in rows of 64: item i of lane l is entry i * 64 + l of it
+  unsigned key[IPT];
+  unsigned long long rec[IPT];
+  unsigned rank[IPT];
+  const int wbase = tile_base + w * (IPT * 64) + lane;
+#pragma unroll
+  for (int i = 0; i < IPT; ++i) {
+    const int idx = wbase + i * 64;
+    const bool v = idx < n;
+    key[i] = v ? (unsigned)keys_in[idx] : 0u;
+    rec[i] = v ? rec_in[idx] : 0ull;
+  }
+
+  // rank within the wave's chunk, row by row: the entries of a row with the
+  // same digit find each other (m: every lane ORs its bit into the digit's
+  // word of the wave's mask table and reads the word back; the eight-ballot
+  // form measured 2 us slower per pass), each ranks itself behind the wave's count
+  // of that digit so far plus its peers in lower lanes, and the lowest peer
+  // advances the count. LDS serves a wave's accesses in program order; the
+  // wavefront-scope fences emit nothing and keep the compiler from moving or
+  // reusing the accesses across rows.
+  unsigned* mycnt = wcnt + w * kOsRadix;
+  unsigned long long* mymask = wmask + w * kOsRadix;
+  const unsigned long long lane_bit = 1ull << lane;
+  const unsigned long long lanes_below = lane_bit - 1ull;
+#pragma unroll
+  for (int i = 0; i < IPT; ++i) {
+    const bool v = wbase + i * 64 < n;
+    const unsigned d = ((key[i] & keymask) >> shift) & 255u;
+    if (v) atomicOr(&mymask[d], lane_bit);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const unsigned long long m = v ? mymask[d] : 0ull;
+    const unsigned below = __popcll(m & lanes_below);
+    unsigned prev = 0;
+    if (v) prev = mycnt[d];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (v && below == 0) {
+      mycnt[d] = prev + (unsigned)__popcll(m);
+      mymask[d] = 0ull;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    rank[i] = prev + below;
+  }
+  __syncthreads();
+
+  // digit d (thread d): tile count, and the per-wave counters turned into
+  // exclusive prefixes over the waves
+  unsigned cnt = 0;
+  if (tid < kOsRadix) {
+    for (int k = 0; k < NW; ++k) {
+      const unsigned c = wcnt[k * kOsRadix + tid];
+      wcnt[k * kOsRadix + tid] = cnt;
+      cnt += c;
+    }
+    if (tile != 0)
+      __hip_atomic_store(&state[(size_t)tile * kOsRadix + tid],
+                         kOsAggregate | cnt, OS_RLX_AGENT);
+  }
+  const unsigned lb = os_scan256(cnt, wsum_a, tid);
+  if (tid < kOsRadix) lbase[tid] = lb;
+  // tile 0 scans this place's histogram: its prefix carries the digit bases
+  unsigned excl = 0;
+  if (tile == 0)
+    excl = os_scan256(tid < kOsRadix ? ghist[tid] : 0u, wsum_b, tid);
+  __syncthreads();
+
+  // place of every entry in the tile ordered by digit; the counters' bytes
+  // then become the reorder buffers
+#pragma unroll
+  for (int i = 0; i < IPT; ++i) {
+    const unsigned d = ((key[i] & keymask) >> shift) & 255u;
+    rank[i] += lbase[d] + wcnt[w * kOsRadix + d];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < IPT; ++i) {
+    if (wbase + i * 64 < n && rank[i] < (unsigned)TILE) {
+      lkeys[rank[i]] = key[i];
+      lrec[rank[i]] = rec[i];
+    }
+  }
+
+  // look-back over lower tickets, one digit per thread; a round loads the
+  // next kOsWindow states at once (independent loads) and walks them in order
+  if (tid < kOsRadix) {
+    bool fail = false;
+    if (tile != 0) {
+      int t = tile - 1;
+      unsigned spins = 0;
+      for (;;) {
+        unsigned s[kOsWindow];
+#pragma unroll
+        for (int k = 0; k < kOsWindow; ++k)
+          s[k] = t - k >= 0 ? __hip_atomic_load(
+                                  &state[(size_t)(t - k) * kOsRadix + tid],
+                                  OS_RLX_AGENT)
+                            : 0u;
+        int used = 0;
+        bool done = false;
+#pragma unroll
+        for (int k = 0; k < kOsWindow; ++k) {
+          const unsigned st = s[k] >> 30;
+          if (!done && used == k && st != 0u) {
+            excl += s[k] & kOsCountMask;
+            used = k + 1;
+            done = st == 2u;
+          }
+        }
+        if (done) break;
+        t -= used;
+        if (t < 0) {  // tile 0 only ever publishes a prefix
+          fail = true;
+          break;
+        }
+        if (used == 0) {
+          ++spins;
+          if (spins >= kOsSpinLimit ||
+              ((spins & 1023u) == 0u &&
+               __hip_atomic_load(status, OS_RLX_AGENT) != 0)) {
+            fail = true;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
+        }
+      }
+    }
+    if (fail) {
+      atomicOr(status, 1);
+      misc[1] = 1u;
+    } else {
+      __hip_atomic_store(&state[(size_t)tile * kOsRadix + tid],
+                         kOsPrefix | ((excl + cnt) & kOsCountMask),
+                         OS_RLX_AGENT);
+    }
+    off[tid] = (int)(excl - lb);
+  }
+  __syncthreads();
+  if (misc[1]) return;
+
+  // entry j of the reordered tile goes to (digit base + tiles before) + its
+  // place in the tile's run of that digit
+  for (int j = tid; j < valid_n; j += THREADS) {
+    const unsigned k = lkeys[j];
+    const unsigned d = ((k & keymask) >> shift) & 255u;
+    const int dst = off[d] + j;
+    if ((unsigned)dst < (unsigned)n) {
+      keys_out[dst] = (int)k;
+      rec_out[dst] = lrec[j];
+    }
+  }
+}
+
+template <int THREADS, int IPT>
+void os_scatter_launch(int tiles, const int* keys_in, const SortRec* rec_in,
+                       int* keys_out, SortRec* rec_out, int n, int shift,
+                       unsigned keymask, const unsigned* ghist,
+                       unsigned* ticket, unsigned* state, int* status,
+                       hipStream_t stream) {
+  constexpr int smem = os_smem_bytes<THREADS, IPT>();
+  static_assert(smem <= 160 * 1024, "tile does not fit the LDS");
+  auto kernel = onesweep_scatter_kernel<THREADS, IPT>;
+  if (smem > 64 * 1024) {
+    static const hipError_t raised = hipFuncSetAttribute(
+        (const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    LCTR_CHECK_HIP(raised);
+  }
+  hipLaunchKernelGGL(kernel, dim3(tiles), dim3(THREADS), smem, stream, keys_in,
+                     rec_in, keys_out, rec_out, n, shift, keymask, ghist,
+                     ticket, state, status);
+}
+
+int onesweep_sort_tile() { return kOsThreads * kOsItems; }
+
+static int os_passes(int end_bit) { return (end_bit + 7) / 8; }
+
+// bytes of the work buffer: control block + one state array per pass
+size_t onesweep_sort_work_bytes(int n, int end_bit) {
+  const size_t tile = kOsThreads * kOsItems;
+  const size_t tiles = ((size_t)n + tile - 1) / tile;
+  return (size_t)kOsCtrlWords * 4 +
+         (size_t)os_passes(end_bit) * tiles * kOsRadix * 4;
+}
+
+// keys_in is never written; keys_tmp / rec_tmp (n entries each) are needed
+// from two passes on. The passes ping-pong so that the last one lands in the
+// output pair.
+void onesweep_sort_rec_launch(void* work, const int* keys_in, int* keys_out,
+                              int* keys_tmp, const int* rec_in, int* rec_out,
+                              int* rec_tmp, int n, int end_bit, int* status,
+                              hipStream_t stream) {
+  if (n <= 0) return;
+  const int passes = os_passes(end_bit);
+  const int tile = kOsThreads * kOsItems;
+  const int tiles = (n + tile - 1) / tile;
+  const unsigned keymask = (1u << end_bit) - 1u;
+  unsigned* ghist = (unsigned*)work;
+  unsigned* tickets = ghist + kOsMaxPasses * kOsRadix;
+  unsigned* state = ghist + kOsCtrlWords;
+  const size_t pass_words = (size_t)tiles * kOsRadix;
+  LCTR_CHECK_HIP(hipMemsetAsync(work, 0, (size_t)kOsCtrlWords * 4, stream));
+  const int hist_blocks = std::min(
+      kOsHistMaxBlocks,
+      (n + kOsHistMaxThreads * 8 - 1) / (kOsHistMaxThreads * 8));
+  hipLaunchKernelGGL(onesweep_hist_kernel, dim3(hist_blocks),
+                     dim3(kOsHistMaxThreads), 0, stream, keys_in, n, passes,
+                     keymask, ghist, (uint4*)state,
+                     (long)(passes * pass_words / 4));
+  const int* ksrc = keys_in;
+  const SortRec* rsrc = (const SortRec*)rec_in;
+  for (int p = 0; p < passes; ++p) {
+    const bool to_out = ((passes - 1 - p) & 1) == 0;
+    int* kdst = to_out ? keys_out : keys_tmp;
+    SortRec* rdst = (SortRec*)(to_out ? rec_out : rec_tmp);
+    os_scatter_launch<kOsThreads, kOsItems>(
+        tiles, ksrc, rsrc, kdst, rdst, n, 8 * p, keymask,
+        ghist + p * kOsRadix, tickets + p, state + p * pass_words, status,
+        stream);
+    ksrc = kdst;
+    rsrc = rdst;
+  }
 }
 
 // ---------------------------------------------------------------------------
