@@ -205,8 +205,10 @@ at::Tensor inv_perm_i32(at::Tensor perm_in) {
   CHK(perm.is_cuda(), "perm must be on GPU");
   const int n = (int)perm.numel();
   auto inv = at::empty({n}, perm.options());
+  if (n == 0) return inv;
   lightctr::inv_perm_launch(perm.data_ptr<int>(), inv.data_ptr<int>(), n,
                             cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return inv;
 }
 
@@ -686,7 +688,38 @@ void ps_apply(at::Tensor lidx, at::Tensor gW, at::Tensor gV, at::Tensor W,
               c10::optional<at::Tensor> shadowV, int64_t updater, double lr,
               double lam, double eps) {
   CHK(lidx.is_cuda() && lidx.scalar_type() == at::kLong, "lidx i64 GPU");
+  CHK(lidx.dim() == 1 && lidx.is_contiguous(),
+      "lidx must be 1-D and contiguous");
+  CHK(updater >= 0 && updater <= 3, "updater must be 0..3, got ", updater);
+  check_cuda_f32(W, "W");
+  check_cuda_f32(V, "V");
+  check_cuda_f32(gW, "gW");
+  check_cuda_f32(gV, "gV");
+  CHK(W.dim() == 1, "W must be [F]");
+  CHK(V.dim() == 2 && V.size(0) == W.size(0), "V must be [F, K]");
+  const long n = lidx.numel();
   const int K = (int)V.size(1);
+  CHK(gW.dim() == 1 && gW.size(0) == n, "gW must be [n]");
+  CHK(gV.dim() == 2 && gV.size(0) == n && gV.size(1) == K,
+      "gV must be [n, K]");
+  // every optional state array has the shape of the table it shadows
+  auto check_like = [](const c10::optional<at::Tensor>& t,
+                       const at::Tensor& ref, const char* name) {
+    if (!t.has_value()) return;
+    check_cuda_f32(*t, name);
+    CHK(t->sizes() == ref.sizes(), name, " shape mismatch");
+  };
+  check_like(nW, W, "nW");
+  check_like(nV, V, "nV");
+  check_like(shadowW, W, "shadowW");
+  check_like(shadowV, V, "shadowV");
+  if (updater == 1 || updater == 3)
+    CHK(nW.has_value() && nV.has_value(),
+        "adagrad / dcasgda need nW and nV");
+  if (updater >= 2)
+    CHK(shadowW.has_value() && shadowV.has_value(),
+        "dcasgd / dcasgda need shadowW and shadowV");
+  if (n == 0) return;
   lightctr::ps_apply_launch(
       lidx.data_ptr<long>(), (int)lidx.numel(), gW.data_ptr<float>(),
       gV.data_ptr<float>(), W.data_ptr<float>(), V.data_ptr<float>(),
@@ -695,6 +728,7 @@ void ps_apply(at::Tensor lidx, at::Tensor gW, at::Tensor gV, at::Tensor W,
       shadowW.has_value() ? shadowW->data_ptr<float>() : nullptr,
       shadowV.has_value() ? shadowV->data_ptr<float>() : nullptr, K,
       (int)updater, (float)lr, (float)lam, (float)eps, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 // ---- PS dense table (flat slab; payload fp32 | fp16 | uint8 codes) ----
@@ -857,33 +891,52 @@ std::vector<at::Tensor> wg_probe(at::Tensor g, int64_t ld, int64_t mode) {
   return {out_lds, out_frag};
 }
 
+// output extent of a k x k window at the given stride and padding; a
+// geometry with no output position is an error, not an empty launch
+void conv_out_shape(int64_t H, int64_t W, int64_t k, int64_t stride,
+                    int64_t pad, int* OH, int* OW) {
+  CHK(k >= 1 && stride >= 1, "conv: k and stride must be >= 1, got k=", k,
+      " stride=", stride);
+  CHK(pad >= 0, "conv: pad must be >= 0, got ", pad);
+  CHK(H + 2 * pad >= k && W + 2 * pad >= k, "conv: a ", k, "x", k,
+      " window does not fit a ", H, "x", W, " image with pad ", pad);
+  *OH = (int)((H + 2 * pad - k) / stride + 1);
+  *OW = (int)((W + 2 * pad - k) / stride + 1);
+}
+
 at::Tensor im2col_bf16(at::Tensor x, int64_t k, int64_t stride,
                        int64_t pad) {
   check_cuda_f32(x, "x");
   CHK(x.dim() == 4, "x must be [B,C,H,W]");
   const int B = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
             W = (int)x.size(3);
-  const int OH = (int)((H + 2 * pad - k) / stride + 1);
-  const int OW = (int)((W + 2 * pad - k) / stride + 1);
+  int OH, OW;
+  conv_out_shape(H, W, k, stride, pad, &OH, &OW);
   auto col = at::empty({(long)B * OH * OW, (long)C * k * k},
                        x.options().dtype(at::kBFloat16));
+  if (col.numel() == 0) return col;
   lightctr::im2col_bf16_launch(x.data_ptr<float>(), col.data_ptr(), B, C, H,
                                W, (int)k, (int)stride, (int)pad, OH, OW,
                                cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return col;
 }
 
 at::Tensor col2im(at::Tensor dcol, int64_t B, int64_t C, int64_t H,
                   int64_t W, int64_t k, int64_t stride, int64_t pad) {
   check_cuda_f32(dcol, "dcol");
-  const int OH = (int)((H + 2 * pad - k) / stride + 1);
-  const int OW = (int)((W + 2 * pad - k) / stride + 1);
-  CHK(dcol.size(0) == (long)B * OH * OW && dcol.size(1) == C * k * k,
+  CHK(B >= 0 && C >= 0 && H >= 1 && W >= 1, "col2im: bad image shape");
+  int OH, OW;
+  conv_out_shape(H, W, k, stride, pad, &OH, &OW);
+  CHK(dcol.dim() == 2 && dcol.size(0) == (long)B * OH * OW &&
+          dcol.size(1) == C * k * k,
       "dcol shape mismatch");
   auto dx = at::empty({B, C, H, W}, dcol.options());
+  if (dx.numel() == 0) return dx;
   lightctr::col2im_launch(dcol.data_ptr<float>(), dx.data_ptr<float>(),
                           (int)B, (int)C, (int)H, (int)W, (int)k,
                           (int)stride, (int)pad, OH, OW, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return dx;
 }
 
@@ -893,35 +946,48 @@ void auc_hist_add(at::Tensor pred, at::Tensor label, at::Tensor hist) {
   CHK(hist.is_cuda() && hist.scalar_type() == at::kInt &&
           hist.is_contiguous(),
       "hist must be cuda int32 [2*buckets]");
+  CHK(hist.numel() >= 2 && hist.numel() % 2 == 0,
+      "hist must hold 2*buckets counts, buckets >= 1");
+  CHK(label.numel() == pred.numel(), "pred and label lengths differ");
   const int buckets = (int)(hist.numel() / 2);
+  if (pred.numel() == 0) return;
   lightctr::auc_hist_add_launch(pred.data_ptr<float>(),
                                 label.data_ptr<float>(),
                                 (long)pred.numel(),
                                 (unsigned int*)hist.data_ptr(), buckets,
                                 cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 at::Tensor auc_scan(at::Tensor hist) {
   CHK(hist.is_cuda() && hist.scalar_type() == at::kInt &&
           hist.is_contiguous(),
       "hist must be cuda int32 [2*buckets]");
+  CHK(hist.numel() >= 2 && hist.numel() % 2 == 0,
+      "hist must hold 2*buckets counts, buckets >= 1");
   const int buckets = (int)(hist.numel() / 2);
   auto out = at::zeros({3}, hist.options().dtype(at::kDouble));
   lightctr::auc_scan_launch((const unsigned int*)hist.data_ptr(), buckets,
                             out.data_ptr<double>(), cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return out;  // {correct-pair mass, P, N}
 }
 
 at::Tensor bitmap_compact(at::Tensor bitmap, at::Tensor out_fids,
                           at::Tensor out_count) {
   CHK(bitmap.is_cuda() && bitmap.is_contiguous(), "bitmap");
+  CHK(bitmap.scalar_type() == at::kLong,
+      "bitmap must be int64 (one 64-feature word per element)");
   check_cuda_i32(out_fids, "out_fids");
   check_cuda_i32(out_count, "out_count");
+  CHK(out_count.numel() >= 1, "out_count must hold the counter");
+  if (bitmap.numel() == 0) return out_count;
   lightctr::bitmap_compact_launch((unsigned long long*)bitmap.data_ptr(),
                                   (int)bitmap.numel(),
                                   out_fids.data_ptr<int>(),
                                   out_count.data_ptr<int>(),
                                   (int)out_fids.numel(), cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return out_count;
 }
 
@@ -1341,15 +1407,25 @@ at::Tensor w2v_negsample_step(at::Tensor E, at::Tensor O,
   check_cuda_f32(O, "O");
   CHK(centers.scalar_type() == at::kLong, "centers i64");
   const int B = (int)centers.numel();
+  CHK(E.dim() == 2 && O.dim() == 2 && O.size(1) == E.size(1),
+      "E and O must be [V, D]");
+  for (const at::Tensor* t : {&centers, &ctx, &negs})
+    CHK(t->is_cuda() && t->scalar_type() == at::kLong && t->is_contiguous(),
+        "centers, ctx and negs must be contiguous int64 GPU tensors");
+  CHK(ctx.dim() == 2 && ctx.size(0) == B && ctx.size(1) >= 1,
+      "ctx must be [B, C] with C >= 1");
+  CHK(negs.dim() == 2 && negs.size(0) == B, "negs must be [B, N]");
   const int C = (int)ctx.size(1);
   const int N = (int)negs.size(1);
   const int D = (int)E.size(1);
   CHK(D <= 64, "w2v kernel supports dim <= 64");
   auto loss = at::empty({B}, E.options());
+  if (B == 0) return loss;
   lightctr::w2v_negsample_launch(
       E.data_ptr<float>(), O.data_ptr<float>(), centers.data_ptr<long>(),
       ctx.data_ptr<long>(), negs.data_ptr<long>(), loss.data_ptr<float>(),
       B, C, N, D, (float)lr, (float)scale, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return loss;
 }
 
@@ -1474,46 +1550,71 @@ std::vector<at::Tensor> parse_libffm(const std::string& path,
 
 // ---- codecs ----
 
+// the kernels stage the table in LDS and emit one uint8 code per value
+void check_quantile_table(const at::Tensor& table) {
+  check_cuda_f32(table, "table");
+  CHK(table.numel() >= 1 && table.numel() <= 256,
+      "quantile table must hold 1..256 levels, got ", table.numel());
+}
+
 at::Tensor quantile_encode(at::Tensor x, at::Tensor table) {
   check_cuda_f32(x, "x");
-  check_cuda_f32(table, "table");
+  check_quantile_table(table);
   auto code = at::empty(x.sizes(), x.options().dtype(at::kByte));
+  if (x.numel() == 0) return code;
   lightctr::quantile_encode_launch(x.data_ptr<float>(),
                                    code.data_ptr<unsigned char>(),
                                    table.data_ptr<float>(),
                                    (int)table.numel(), x.numel(),
                                    cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return code;
 }
 
 at::Tensor quantile_decode(at::Tensor code, at::Tensor table) {
-  check_cuda_f32(table, "table");
+  check_quantile_table(table);
+  CHK(code.is_cuda(), "code must be on GPU");
+  CHK(code.scalar_type() == at::kByte, "code must be uint8");
+  CHK(code.is_contiguous(), "code must be contiguous");
   auto x = at::empty(code.sizes(), table.options());
+  if (code.numel() == 0) return x;
   lightctr::quantile_decode_launch(code.data_ptr<unsigned char>(),
                                    x.data_ptr<float>(),
                                    table.data_ptr<float>(),
                                    (int)table.numel(), code.numel(),
                                    cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return x;
 }
 
 at::Tensor lowbit_encode(at::Tensor x, double thresh, int64_t bits) {
   check_cuda_f32(x, "x");
+  CHK(bits == 1 || bits == 2, "lowbit: bits must be 1 or 2, got ", bits);
   const long n = x.numel();
   const long nw = (n * bits + 31) / 32;
   auto words = at::empty({nw}, x.options().dtype(at::kInt));
+  if (n == 0) return words;
   lightctr::lowbit_encode_launch(x.data_ptr<float>(),
                                  (unsigned int*)words.data_ptr(),
                                  (float)thresh, (int)bits, n, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return words;
 }
 
 at::Tensor lowbit_decode(at::Tensor words, double lo, double hi, int64_t bits,
                          int64_t n) {
+  CHK(bits == 1 || bits == 2, "lowbit: bits must be 1 or 2, got ", bits);
+  check_cuda_i32(words, "words");
+  CHK(n >= 0, "lowbit: n must be >= 0, got ", n);
+  CHK(words.numel() >= (n * bits + 31) / 32, "lowbit: ", n, " values at ",
+      bits, " bits need ", (n * bits + 31) / 32, " words, got ",
+      words.numel());
   auto x = at::empty({n}, words.options().dtype(at::kFloat));
+  if (n == 0) return x;
   lightctr::lowbit_decode_launch((const unsigned int*)words.data_ptr(),
                                  x.data_ptr<float>(), (float)lo, (float)hi,
                                  (int)bits, n, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return x;
 }
 
@@ -1523,13 +1624,22 @@ at::Tensor gbm_hist(at::Tensor bins, at::Tensor grad, at::Tensor hess,
   check_cuda_f32(grad, "grad");
   check_cuda_f32(hess, "hess");
   check_cuda_i32(node_of_row, "node_of_row");
+  CHK(bins.dim() == 2 && bins.is_contiguous(),
+      "bins must be a contiguous [N, D] tensor");
+  // one grid row per node: gridDim.y stops at 65535
+  CHK(n_nodes >= 1 && n_nodes <= 65535,
+      "gbm_hist: n_nodes must be in 1..65535, got ", n_nodes);
   const int N = (int)bins.size(0), D = (int)bins.size(1);
+  CHK(grad.numel() == N && hess.numel() == N && node_of_row.numel() == N,
+      "grad, hess and node_of_row must each hold N = ", N, " entries");
   auto hist = at::zeros({n_nodes, D, 256, 2}, grad.options());
+  if (N == 0 || D == 0) return hist;
   lightctr::gbm_hist_launch(bins.data_ptr<unsigned char>(),
                             grad.data_ptr<float>(), hess.data_ptr<float>(),
                             node_of_row.data_ptr<int>(),
                             hist.data_ptr<float>(), N, D, (int)n_nodes,
                             cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return hist;
 }
 

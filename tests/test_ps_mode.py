@@ -210,3 +210,4 @@ def test_ps_apply_kernel_parity(updater):
         assert torch.allclose(nV, rnV, atol=1e-6)
     if updater.startswith("dcasgd"):
         assert torch.allclose(shV, rshV, atol=1e-5)
+        assert torch.allclose(shW, rshW, atol=1e-5)
