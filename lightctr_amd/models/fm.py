@@ -7,9 +7,11 @@ Adagrad apply) — rebuilt GPU-first:
 
   * parameters W [F] and V [F,K] are flat fp32 slabs resident in HBM3E
   * the train step is a handful of HIP kernel launches with no device->host
-    syncs. Default backward_mode="segment": training forward (loss and
-    per-entry (row, x) records fused in), radix sort with the records as
-    payload, and a tile-local segment reduce: every block finds the pieces
+    syncs. Default backward_mode="segment": training forward (loss fused
+    in) beside a radix sort of the fids that makes and carries one (row, x)
+    record per entry (overlap_sort; the sort reads only the batch and runs
+    on a second stream), and a tile-local segment reduce: every block
+    finds the pieces
     of its own tile of sorted entries, recomputes the gradients and applies
     the optimizer in place. "segment_list" (the per-piece reduce fed by a
     global work list), "segment_emit" (that reduce fed by a per-entry
@@ -29,7 +31,8 @@ from dataclasses import dataclass
 import torch
 
 from ..ops import fm_ref
-from ..ops._extension import require_hip_ops, sort_ids, sort_ids_rec
+from ..ops._extension import (require_hip_ops, sort_end_bit, sort_ids,
+                              sort_ids_rec)
 from ..utils.checks import validate_csr_batch
 from ..utils.metrics import auc_score
 
@@ -119,6 +122,15 @@ class FMModel:
         self.sort_impl = "onesweep"
         self.sort_status = torch.zeros(1, dtype=torch.int32,
                                        device=self.device)
+        # front half of "segment" / "segment_list" with the onesweep sort.
+        # True: the sort makes the records itself (row-walking histogram)
+        # and runs on a pool stream beside a forward that writes none; the
+        # two join in front of the reduce. "serial": the same launches in
+        # sequence on one stream. False: the forward writes the records and
+        # the sort follows it (the earlier sequence). All three hand the
+        # reduce a bit-identical sorted stream; measurements in
+        # profiles/r7_01_fm_overlap.txt.
+        self.overlap_sort = True
         if self._use_hip:
             require_hip_ops()  # fail loudly if extension missing on GPU
 
@@ -150,6 +162,22 @@ class FMModel:
                     and not self.fused_apply):
                 tiled = (self.backward_mode == "segment"
                          and self._cap_tiles(ops))
+                end_bit = sort_end_bit(self.h.num_features)
+                if (self.overlap_sort and self.sort_impl == "onesweep"
+                        and end_bit <= 31 and fids.numel() < (1 << 30)):
+                    # the sort makes the records itself and needs nothing
+                    # of the model: one call enqueues it and the forward,
+                    # on two streams unless overlap_sort == "serial"
+                    loss, dpred, sumVX, sorted_fids, sorted_rec = (
+                        ops.fm_forward_train_sorted(
+                            row_ptr, fids, vals, self.W, self.V, labels,
+                            scale, end_bit,
+                            reset=self.count if tiled else None,
+                            status=self.sort_status,
+                            overlap=self.overlap_sort != "serial"))
+                    self._segment_reduce(ops, sorted_fids, sorted_rec, sumVX,
+                                         dpred, tiled)
+                    return loss
                 # the work-list pass resets the spill counter; without it
                 # the forward does
                 loss, dpred, sumVX, rec = ops.fm_forward_train(
@@ -300,6 +328,15 @@ class FMModel:
         sorted_fids, sorted_rec = sort_ids_rec(
             fids, rec, self.h.num_features, impl=self.sort_impl,
             status=self.sort_status)
+        self._segment_reduce(ops, sorted_fids, sorted_rec, sumVX, dpred,
+                             tiled)
+
+    def _segment_reduce(self, ops, sorted_fids, sorted_rec, sumVX, dpred,
+                        tiled):
+        """Back half of the segment modes: reduce over the sorted stream,
+        then the optimizer over the spilled runs."""
+        if sorted_fids.numel() == 0:
+            return
         spill, tail, kw = self._segment_pieces(ops, sorted_fids,
                                                worklist=not tiled)
         reduce = (ops.fm_segment_tile_rec if tiled

@@ -46,11 +46,16 @@ class _LazyOps:
 hip_ops = _LazyOps()
 
 
+def sort_end_bit(upper: int) -> int:
+    """Bits a radix sort has to look at for ids known to be < upper."""
+    return max(1, int(upper - 1).bit_length())
+
+
 def sort_ids(fids, upper: int):
     """(sorted, perm int64) for nonnegative int32 ids known to be < upper —
     drop-in for torch.sort(fids) on the GPU hot path, but radix-sorts only
     the live bit range (2-3 passes instead of 4; see sort_kernels.hip)."""
-    end_bit = max(1, int(upper - 1).bit_length())
+    end_bit = sort_end_bit(upper)
     return require_hip_ops().radix_sort_index(fids, end_bit)
 
 
@@ -67,7 +72,7 @@ def sort_ids_rec(fids, rec, upper: int, impl: str = "onesweep", status=None):
     if impl not in ("onesweep", "rocprim"):
         raise ValueError(f"unknown sort impl {impl!r}")
     ops = require_hip_ops()
-    end_bit = max(1, int(upper - 1).bit_length())
+    end_bit = sort_end_bit(upper)
     if impl == "onesweep" and end_bit <= 31 and fids.numel() < (1 << 30):
         return ops.onesweep_sort_rec(fids, rec, end_bit, status)
     return ops.radix_sort_rec(fids, rec, end_bit)

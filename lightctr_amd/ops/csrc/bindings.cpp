@@ -2,6 +2,7 @@
 // the native data loader. Host-only translation unit.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <ATen/cuda/CUDAEvent.h>
 #include <c10/cuda/CUDAException.h>
 
 #include <cstdint>
@@ -1307,6 +1308,148 @@ std::vector<at::Tensor> onesweep_sort_rec(at::Tensor keys, at::Tensor rec,
   return {sorted, sorted_rec};
 }
 
+// The records of a CSR batch on their own: rec[j] = {row of j, bits of
+// vals[j]}, what fm_forward_train returns as its fourth output.
+at::Tensor fm_records(at::Tensor row_ptr, at::Tensor vals) {
+  check_cuda_i32(row_ptr, "row_ptr");
+  check_cuda_f32(vals, "vals");
+  CHK(row_ptr.numel() >= 1, "row_ptr must hold B + 1 offsets");
+  const int B = (int)row_ptr.numel() - 1;
+  auto rec = at::empty({vals.numel(), 2}, row_ptr.options());
+  if (vals.numel() == 0) return rec;
+  lightctr::fm_records_launch(row_ptr.data_ptr<int>(), vals.data_ptr<float>(),
+                              rec.data_ptr<int>(), B, cur_stream());
+  return rec;
+}
+
+// what the onesweep sort of a CSR batch accepts, and its buffers
+struct CsrSortBuffers {
+  at::Tensor sorted, sorted_rec, work, keys_tmp, rec_tmp, status;
+};
+
+void check_csr_sort(const at::Tensor& row_ptr, const at::Tensor& fids,
+                    const at::Tensor& vals, int64_t end_bit,
+                    const c10::optional<at::Tensor>& status) {
+  check_cuda_i32(row_ptr, "row_ptr");
+  check_cuda_i32(fids, "fids");
+  check_cuda_f32(vals, "vals");
+  CHK(row_ptr.numel() >= 1, "row_ptr must hold B + 1 offsets");
+  CHK(vals.numel() == fids.numel(), "vals must have one value per entry");
+  CHK(end_bit >= 1 && end_bit <= 31, "end_bit in [1,31]");
+  CHK(fids.numel() < (1L << 30), "n must be below 2^30");
+  if (status.has_value()) {
+    check_cuda_i32(*status, "status");
+    CHK(status->numel() >= 1, "status must hold one word");
+  }
+}
+
+// every allocation of the sort, on the current stream
+CsrSortBuffers alloc_csr_sort(const at::Tensor& fids, int64_t end_bit,
+                              const c10::optional<at::Tensor>& status) {
+  CsrSortBuffers b;
+  const long n = fids.numel();
+  b.sorted = at::empty_like(fids);
+  b.sorted_rec = at::empty({n, 2}, fids.options());
+  if (n == 0) return b;
+  b.status = status.has_value() ? *status : at::zeros({1}, fids.options());
+  const unsigned long bytes =
+      lightctr::onesweep_sort_work_bytes((int)n, (int)end_bit);
+  b.work = at::empty({(long)bytes}, fids.options().dtype(at::kByte));
+  b.rec_tmp = at::empty({n, 2}, fids.options());
+  if (end_bit > 8) b.keys_tmp = at::empty_like(fids);
+  return b;
+}
+
+void launch_csr_sort(const CsrSortBuffers& b, const at::Tensor& row_ptr,
+                     const at::Tensor& fids, const at::Tensor& vals,
+                     int64_t end_bit, ihipStream_t* stream) {
+  lightctr::onesweep_sort_csr_launch(
+      b.work.data_ptr(), row_ptr.data_ptr<int>(), fids.data_ptr<int>(),
+      vals.data_ptr<float>(), (int)row_ptr.numel() - 1,
+      b.sorted.data_ptr<int>(),
+      end_bit > 8 ? b.keys_tmp.data_ptr<int>() : nullptr,
+      b.sorted_rec.data_ptr<int>(), b.rec_tmp.data_ptr<int>(),
+      (int)fids.numel(), (int)end_bit, b.status.data_ptr<int>(), stream);
+}
+
+// onesweep_sort_rec(fids, fm_records(row_ptr, vals)) without the records'
+// own launch: the histogram kernel walks the rows and writes them.
+std::vector<at::Tensor> onesweep_sort_csr(at::Tensor row_ptr, at::Tensor fids,
+                                          at::Tensor vals, int64_t end_bit,
+                                          c10::optional<at::Tensor> status) {
+  check_csr_sort(row_ptr, fids, vals, end_bit, status);
+  auto b = alloc_csr_sort(fids, end_bit, status);
+  if (fids.numel() > 0 && row_ptr.numel() > 1)
+    launch_csr_sort(b, row_ptr, fids, vals, end_bit, cur_stream());
+  return {b.sorted, b.sorted_rec};
+}
+
+// Front half of the segment-mode training step: the training forward (no
+// records) and the record sort of the batch. The sort reads only the batch,
+// so with overlap it runs on a pool stream beside the forward: fork by an
+// event on the current stream, join by an event on the pool stream, no sync
+// and no host read, so a stream capture records the two as parallel branches
+// that meet in front of whatever the caller enqueues next. Everything is
+// allocated on the current stream before the fork, and the join orders every
+// use of the temporaries before their blocks can be handed out again.
+// Both branches are kernels only (the CSR sort zeroes its control block with
+// a kernel, not a memset). The sort branch is enqueued first and the pool
+// stream has the default priority (profiles/r7_01_fm_overlap.txt).
+// overlap=false: the same launches in sequence on the current stream.
+// Returns (loss, dpred, sumVX, sorted_fids, sorted_rec).
+std::vector<at::Tensor> fm_forward_train_sorted(
+    at::Tensor row_ptr, at::Tensor fids, at::Tensor vals, at::Tensor W,
+    at::Tensor V, at::Tensor label, double scale, int64_t end_bit,
+    c10::optional<at::Tensor> reset, c10::optional<at::Tensor> status,
+    bool overlap) {
+  check_csr_sort(row_ptr, fids, vals, end_bit, status);
+  check_cuda_f32(W, "W");
+  check_cuda_f32(V, "V");
+  check_cuda_f32(label, "label");
+  const int B = (int)row_ptr.numel() - 1;
+  const int K = (int)V.size(1);
+  const long nnz = fids.numel();
+  CHK(label.numel() == B, "label must have one value per row");
+  int* reset_ptr = nullptr;
+  if (reset.has_value()) {
+    check_cuda_i32(*reset, "reset");
+    CHK(reset->numel() >= 1, "reset must hold one int");
+    reset_ptr = reset->data_ptr<int>();
+    if (B <= 0) reset->zero_();  // nothing is launched for an empty batch
+  }
+  auto loss = at::empty({B}, W.options());
+  auto dpred = at::empty({B}, W.options());
+  auto sumVX = at::empty({B, K}, W.options());
+  auto b = alloc_csr_sort(fids, end_bit, status);
+  if (B <= 0) return {loss, dpred, sumVX, b.sorted, b.sorted_rec};
+  const auto forward = [&](ihipStream_t* stream) {
+    lightctr::fm_forward_train_launch(
+        row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
+        W.data_ptr<float>(), V.data_ptr<float>(), label.data_ptr<float>(),
+        (float)scale, loss.data_ptr<float>(), dpred.data_ptr<float>(),
+        sumVX.data_ptr<float>(), nullptr, B, K, reset_ptr, stream);
+  };
+  if (nnz == 0) {  // rows without entries: a loss, nothing to sort
+    forward(cur_stream());
+  } else if (!overlap) {
+    forward(cur_stream());
+    launch_csr_sort(b, row_ptr, fids, vals, end_bit, cur_stream());
+  } else {
+    const auto main = at::cuda::getCurrentCUDAStream();
+    const auto side =
+        at::cuda::getStreamFromPool(false, main.device_index());
+    at::cuda::CUDAEvent fork, join;
+    fork.record(main);
+    fork.block(side);
+    launch_csr_sort(b, row_ptr, fids, vals, end_bit,
+                    (ihipStream_t*)side.stream());
+    forward((ihipStream_t*)main.stream());
+    join.record(side);
+    join.block(main);
+  }
+  return {loss, dpred, sumVX, b.sorted, b.sorted_rec};
+}
+
 
 at::Tensor colsum(at::Tensor dZ) {
   check_cuda_f32(dZ, "dZ");
@@ -2033,6 +2176,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("status") = py::none());
   m.def("onesweep_sort_tile", &lightctr::onesweep_sort_tile,
         "entries per tile of onesweep_sort_rec");
+  m.def("fm_records", &fm_records,
+        "records of a CSR batch: rec[j] = (row of j, bits of vals[j])",
+        py::arg("row_ptr"), py::arg("vals"));
+  m.def("onesweep_sort_csr", &onesweep_sort_csr,
+        "onesweep sort of a CSR batch's (fid, record) stream, the records "
+        "made by the histogram kernel -> (sorted, sorted_rec)",
+        py::arg("row_ptr"), py::arg("fids"), py::arg("vals"),
+        py::arg("end_bit"), py::arg("status") = py::none());
+  m.def("fm_forward_train_sorted", &fm_forward_train_sorted,
+        "FM training forward and the record sort of the batch, side by side "
+        "with overlap -> (loss, dpred, sumVX, sorted_fids, sorted_rec)",
+        py::arg("row_ptr"), py::arg("fids"), py::arg("vals"), py::arg("W"),
+        py::arg("V"), py::arg("label"), py::arg("scale"), py::arg("end_bit"),
+        py::arg("reset") = py::none(), py::arg("status") = py::none(),
+        py::arg("overlap") = true);
   m.def("colsum", &colsum, "bias gradient column sum");
   m.def("to_bf16", &to_bf16, "f32 -> bf16 convert");
   m.def("dense_adam", &dense_adam, "dense Adam + bf16 mirror refresh");

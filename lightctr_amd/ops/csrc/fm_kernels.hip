@@ -125,13 +125,16 @@ __device__ __forceinline__ void logloss_grad_row(float z, float y, float scale,
 // Forward: pred[row] = sum_j w[fid]*x + 0.5*(||sumVX||^2 - sum_j ||v*x||^2)
 // Also writes sumVX[row*K+k] (needed by backward).
 // ---------------------------------------------------------------------------
-// Row body shared by the inference and the training forward. TRAIN adds the
+// Row body shared by the inference and the training forward. REC adds the
 // per-entry record rec[j] = {row, bits of vals[j]} (written by the k == 0
 // lane of the feature group that has just loaded vals[j]): the segment
 // backward sorts these records by fid and recomputes each entry's gradient
-// from them, so no per-entry gradient buffer is ever written.
+// from them, so no per-entry gradient buffer is ever written. The records
+// are pure batch data: fm_records_kernel and the row-walking histogram of
+// sort_kernels.hip write the same ones without the model, which lets the
+// sort run beside a forward that has REC off.
 // Returns the row's pred (valid in every lane).
-template <int K, bool TRAIN>
+template <int K, bool REC>
 __device__ __forceinline__ float fm_forward_row(
     const int* __restrict__ row_ptr, const int* __restrict__ fids,
     const float* __restrict__ vals, const float* __restrict__ W,
@@ -162,22 +165,22 @@ __device__ __forceinline__ float fm_forward_row(
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      if (TRAIN && k == 0)
+      if (REC && k == 0)
         rec[j + u * G] = make_int2(row, __float_as_int(x[u]));
       const float vx = v[u] * x[u];
       sVX += vx;
       sV2X2 += vx * vx;
-      lin += w[u] * x[u];
+      lin = fmaf(w[u], x[u], lin);
     }
   }
   for (; j < end; j += G) {
     const int fid = fids[j];
     const float x = vals[j];
-    if (TRAIN && k == 0) rec[j] = make_int2(row, __float_as_int(x));
+    if (REC && k == 0) rec[j] = make_int2(row, __float_as_int(x));
     const float vx = V[(size_t)fid * K + k] * x;
     sVX += vx;
     sV2X2 += vx * vx;
-    if (k == 0) lin += W[fid] * x;
+    if (k == 0) lin = fmaf(W[fid], x, lin);
   }
   // combine feature groups: lanes {k, K+k, 2K+k, ...} sum -> every lane
   // holds the row's total sumVX for its k (replicated G times).
@@ -208,8 +211,8 @@ __global__ void fm_forward_kernel(const int* __restrict__ row_ptr,
 
 // Training forward: the row body above plus, in lane 0, the loss and the
 // upstream gradient of the row (what logloss_grad_kernel computes from a
-// stored pred), and the per-entry records for the segment backward.
-template <int K>
+// stored pred), and, with REC, the per-entry records for the segment backward.
+template <int K, bool REC>
 __global__ void fm_forward_train_kernel(
     const int* __restrict__ row_ptr, const int* __restrict__ fids,
     const float* __restrict__ vals, const float* __restrict__ W,
@@ -222,14 +225,29 @@ __global__ void fm_forward_train_kernel(
   // the spill counter of the segment backward that follows in the stream
   if (reset != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *reset = 0;
   if (row >= B) return;
-  const float p = fm_forward_row<K, true>(row_ptr, fids, vals, W, V, sumVX,
-                                          rec, row, lane);
+  const float p = fm_forward_row<K, REC>(row_ptr, fids, vals, W, V, sumVX,
+                                         rec, row, lane);
   if (lane == 0) {
     float l, d;
     logloss_grad_row(p, label[row], scale, l, d);
     loss[row] = l;
     dpred[row] = d;
   }
+}
+
+// The records alone: rec[j] = {row of j, bits of vals[j]}, one wave per row,
+// lanes striding over the row (empty rows write nothing). Feeds the sorts that
+// do not make the records themselves, and is the reference for the ones that
+// do.
+__global__ void fm_records_kernel(const int* __restrict__ row_ptr,
+                                  const float* __restrict__ vals,
+                                  int2* __restrict__ rec, int B) {
+  const int lane = threadIdx.x & (LCTR_WAVE - 1);
+  const int row = blockIdx.x * (blockDim.x / LCTR_WAVE) + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const int end = row_ptr[row + 1];
+  for (int j = row_ptr[row] + lane; j < end; j += LCTR_WAVE)
+    rec[j] = make_int2(row, __float_as_int(vals[j]));
 }
 
 // ---------------------------------------------------------------------------
@@ -1342,10 +1360,28 @@ void fm_forward_train_launch(const int* row_ptr, const int* fids,
   const int wpb = waves_per_block();
   dim3 block(wpb * LCTR_WAVE);
   dim3 grid((B + wpb - 1) / wpb);
-  DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_train_kernel<KC>), grid, block,
-                                   0, stream, row_ptr, fids, vals, W, V, label,
-                                   scale, loss, dpred, sumVX, (int2*)rec, B,
-                                   reset));
+  // rec == nullptr: the records are made elsewhere, the row body writes none
+  if (rec != nullptr) {
+    DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_train_kernel<KC, true>), grid,
+                                     block, 0, stream, row_ptr, fids, vals, W,
+                                     V, label, scale, loss, dpred, sumVX,
+                                     (int2*)rec, B, reset));
+  } else {
+    DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_train_kernel<KC, false>),
+                                     grid, block, 0, stream, row_ptr, fids,
+                                     vals, W, V, label, scale, loss, dpred,
+                                     sumVX, (int2*)nullptr, B, reset));
+  }
+}
+
+void fm_records_launch(const int* row_ptr, const float* vals, int* rec, int B,
+                       hipStream_t stream) {
+  if (B <= 0) return;
+  const int wpb = waves_per_block();
+  dim3 block(wpb * LCTR_WAVE);
+  dim3 grid((B + wpb - 1) / wpb);
+  hipLaunchKernelGGL(fm_records_kernel, grid, block, 0, stream, row_ptr, vals,
+                     (int2*)rec, B);
 }
 
 void logloss_grad_launch(const float* pred, const float* label, float* loss,

@@ -41,12 +41,15 @@ void fm_segment_apply_launch(const int* sorted_fids, const int* perm,
                              float* nV, float* zV, float p0, float p1,
                              float p2, float p3, float q0, float q1, float q2,
                              int num_cus, ihipStream_t* stream);
-// rec: [n, 2] int32 records {row, bits of x}, 8-byte aligned
+// rec: [n, 2] int32 records {row, bits of x}, 8-byte aligned; nullptr: the
+// forward writes no records (fm_records_launch or the CSR sort makes them)
 void fm_forward_train_launch(const int* row_ptr, const int* fids,
                              const float* vals, const float* W, const float* V,
                              const float* label, float scale, float* loss,
                              float* dpred, float* sumVX, int* rec, int B,
                              int K, int* reset, ihipStream_t* stream);
+void fm_records_launch(const int* row_ptr, const float* vals, int* rec, int B,
+                       ihipStream_t* stream);
 void fm_segment_recompute_launch(
     const int* sorted_fids, const int* rec, const float* sumVX,
     const float* dpred, int B, const int* piece_start, const int* n_pieces,
@@ -346,6 +349,16 @@ int onesweep_sort_tile();
 unsigned long onesweep_sort_work_bytes(int n, int end_bit);
 void onesweep_sort_rec_launch(void* work, const int* keys_in, int* keys_out,
                               int* keys_tmp, const int* rec_in, int* rec_out,
+                              int* rec_tmp, int n, int end_bit, int* status,
+                              ihipStream_t* stream);
+// the same sort of a CSR batch's (fid, {row, bits of x}) stream, n =
+// row_ptr[B]: the histogram kernel makes the records, so nothing of it
+// depends on the model. rec_tmp is needed for every end_bit here, keys_tmp
+// from two passes on. Kernels only: a one-block kernel zeroes the control
+// block in place of the memset
+void onesweep_sort_csr_launch(void* work, const int* row_ptr,
+                              const int* keys_in, const float* vals, int B,
+                              int* keys_out, int* keys_tmp, int* rec_out,
                               int* rec_tmp, int n, int end_bit, int* status,
                               ihipStream_t* stream);
 // work list of the segment backward: compacted piece starts of a sorted

@@ -130,12 +130,14 @@ constexpr int kOsRadix = 256;
 constexpr int kOsMaxPasses = 4;
 constexpr int kOsCtrlWords = kOsMaxPasses * kOsRadix + kOsMaxPasses;
 static_assert(kOsCtrlWords * 4 % 16 == 0, "memset block is 16-byte padded");
+static_assert(kOsCtrlWords / 4 <= 1024, "one block zeroes the control block");
 constexpr unsigned kOsCountMask = 0x3fffffffu;
 constexpr unsigned kOsAggregate = 1u << 30;
 constexpr unsigned kOsPrefix = 2u << 30;
 constexpr unsigned kOsSpinLimit = 1u << 20;
 constexpr int kOsHistMaxThreads = 1024;
 constexpr int kOsHistMaxBlocks = 256;
+constexpr int kOsHistRecMaxBlocks = 512;
 // tile shape and look-back window: the winners of the sweep in
 // profiles/r6_01_fm_sort.txt (tiles of 2048 / 4096 / 8192 entries, 256- and
 // 512-thread blocks, windows of 1..64); only this shape is built
@@ -162,6 +164,74 @@ __global__ __launch_bounds__(kOsHistMaxThreads) void onesweep_hist_kernel(
 #pragma unroll
     for (int p = 0; p < kOsMaxPasses; ++p)
       if (p < passes) atomicAdd(&h[p * kOsRadix + ((k >> (8 * p)) & 255u)], 1u);
+  }
+  __syncthreads();
+  for (int i = tid; i < passes * kOsRadix; i += threads) {
+    const unsigned c = h[i];
+    if (c) atomicAdd(&ghist[i], c);
+  }
+}
+
+// Row-walking variant for a CSR batch: also writes the records the sort
+// carries, rec[j] = {row of j, bits of vals[j]} (what the FM training forward
+// writes with REC on), so the sort needs nothing from the model and no launch
+// of its own for the records. One wave per row, grid-strided over rows; a
+// wave loads the bounds of kOsHistRows rows, then their first 64 entries,
+// before it counts any (independent round trips), and walks what a longer row
+// has left afterwards. Every entry of [0, row_ptr[B]) lies in exactly one
+// row, so the histograms equal onesweep_hist_kernel's for the same keys.
+constexpr int kOsHistRows = 4;
+
+__global__ __launch_bounds__(kOsHistMaxThreads) void onesweep_hist_rec_kernel(
+    const int* __restrict__ row_ptr, const int* __restrict__ keys,
+    const float* __restrict__ vals, int2* __restrict__ rec, int B, int n,
+    int passes, unsigned keymask, unsigned* ghist, uint4* state, long state_vec4) {
+  __shared__ unsigned h[kOsMaxPasses * kOsRadix];
+  const int tid = threadIdx.x, threads = blockDim.x;
+  for (int i = tid; i < passes * kOsRadix; i += threads) h[i] = 0;
+  const long gstride = (long)gridDim.x * threads;
+  for (long i = (long)blockIdx.x * threads + tid; i < state_vec4; i += gstride)
+    state[i] = make_uint4(0u, 0u, 0u, 0u);
+  __syncthreads();
+  const int lane = tid & 63;
+  const int wstride = (int)(gstride >> 6);
+  auto count = [&](unsigned k) {
+    k &= keymask;
+#pragma unroll
+    for (int p = 0; p < kOsMaxPasses; ++p)
+      if (p < passes) atomicAdd(&h[p * kOsRadix + ((k >> (8 * p)) & 255u)], 1u);
+  };
+  for (long row0 = ((long)blockIdx.x * threads + tid) >> 6; row0 < B;
+       row0 += (long)kOsHistRows * wstride) {
+    int row[kOsHistRows], j[kOsHistRows], end[kOsHistRows], k[kOsHistRows],
+        x[kOsHistRows];
+#pragma unroll
+    for (int u = 0; u < kOsHistRows; ++u) {
+      const long r = row0 + (long)u * wstride;
+      const bool live = r < B;
+      row[u] = (int)r;
+      // clamped to the stream: a malformed row_ptr cannot reach past it
+      j[u] = live ? max(row_ptr[r], 0) + lane : 0;
+      end[u] = live ? min(row_ptr[r + 1], n) : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < kOsHistRows; ++u) {
+      if (j[u] < end[u]) {
+        k[u] = keys[j[u]];
+        x[u] = __float_as_int(vals[j[u]]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kOsHistRows; ++u) {
+      if (j[u] < end[u]) {
+        rec[j[u]] = make_int2(row[u], x[u]);
+        count((unsigned)k[u]);
+      }
+      for (int jj = j[u] + 64; jj < end[u]; jj += 64) {
+        rec[jj] = make_int2(row[u], __float_as_int(vals[jj]));
+        count((unsigned)keys[jj]);
+      }
+    }
   }
   __syncthreads();
   for (int i = tid; i < passes * kOsRadix; i += threads) {
@@ -426,9 +496,34 @@ size_t onesweep_sort_work_bytes(int n, int end_bit) {
          (size_t)os_passes(end_bit) * tiles * kOsRadix * 4;
 }
 
+// The scatter passes shared by both front ends. The passes ping-pong so that
+// the last one lands in the output pair.
+static void os_scatter_passes(unsigned* ghist, const int* keys_in,
+                              int* keys_out, int* keys_tmp,
+                              const SortRec* rec_in, SortRec* rec_out,
+                              SortRec* rec_tmp, int n, int passes, int tiles,
+                              unsigned keymask, int* status,
+                              hipStream_t stream) {
+  unsigned* tickets = ghist + kOsMaxPasses * kOsRadix;
+  unsigned* state = ghist + kOsCtrlWords;
+  const size_t pass_words = (size_t)tiles * kOsRadix;
+  const int* ksrc = keys_in;
+  const SortRec* rsrc = rec_in;
+  for (int p = 0; p < passes; ++p) {
+    const bool to_out = ((passes - 1 - p) & 1) == 0;
+    int* kdst = to_out ? keys_out : keys_tmp;
+    SortRec* rdst = to_out ? rec_out : rec_tmp;
+    os_scatter_launch<kOsThreads, kOsItems>(
+        tiles, ksrc, rsrc, kdst, rdst, n, 8 * p, keymask,
+        ghist + p * kOsRadix, tickets + p, state + p * pass_words, status,
+        stream);
+    ksrc = kdst;
+    rsrc = rdst;
+  }
+}
+
 // keys_in is never written; keys_tmp / rec_tmp (n entries each) are needed
-// from two passes on. The passes ping-pong so that the last one lands in the
-// output pair.
+// from two passes on.
 void onesweep_sort_rec_launch(void* work, const int* keys_in, int* keys_out,
                               int* keys_tmp, const int* rec_in, int* rec_out,
                               int* rec_tmp, int n, int end_bit, int* status,
@@ -439,30 +534,58 @@ void onesweep_sort_rec_launch(void* work, const int* keys_in, int* keys_out,
   const int tiles = (n + tile - 1) / tile;
   const unsigned keymask = (1u << end_bit) - 1u;
   unsigned* ghist = (unsigned*)work;
-  unsigned* tickets = ghist + kOsMaxPasses * kOsRadix;
-  unsigned* state = ghist + kOsCtrlWords;
-  const size_t pass_words = (size_t)tiles * kOsRadix;
   LCTR_CHECK_HIP(hipMemsetAsync(work, 0, (size_t)kOsCtrlWords * 4, stream));
   const int hist_blocks = std::min(
       kOsHistMaxBlocks,
       (n + kOsHistMaxThreads * 8 - 1) / (kOsHistMaxThreads * 8));
   hipLaunchKernelGGL(onesweep_hist_kernel, dim3(hist_blocks),
                      dim3(kOsHistMaxThreads), 0, stream, keys_in, n, passes,
-                     keymask, ghist, (uint4*)state,
-                     (long)(passes * pass_words / 4));
-  const int* ksrc = keys_in;
-  const SortRec* rsrc = (const SortRec*)rec_in;
-  for (int p = 0; p < passes; ++p) {
-    const bool to_out = ((passes - 1 - p) & 1) == 0;
-    int* kdst = to_out ? keys_out : keys_tmp;
-    SortRec* rdst = (SortRec*)(to_out ? rec_out : rec_tmp);
-    os_scatter_launch<kOsThreads, kOsItems>(
-        tiles, ksrc, rsrc, kdst, rdst, n, 8 * p, keymask,
-        ghist + p * kOsRadix, tickets + p, state + p * pass_words, status,
-        stream);
-    ksrc = kdst;
-    rsrc = rdst;
-  }
+                     keymask, ghist, (uint4*)(ghist + kOsCtrlWords),
+                     (long)(passes * (size_t)tiles * kOsRadix / 4));
+  os_scatter_passes(ghist, keys_in, keys_out, keys_tmp, (const SortRec*)rec_in,
+                    (SortRec*)rec_out, (SortRec*)rec_tmp, n, passes, tiles,
+                    keymask, status, stream);
+}
+
+// Zeroes the control block in place of the memset: run beside the forward on
+// a second stream, the CSR sort is then kernels only, also as a branch of a
+// captured graph (profiles/r7_01_fm_overlap.txt, section 4).
+__global__ __launch_bounds__(kOsCtrlWords / 4) void onesweep_zero_kernel(
+    uint4* ctrl) {
+  ctrl[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// The same sort fed by a CSR batch (n = row_ptr[B] entries): the histogram
+// kernel makes the records. They are written in CSR order into whichever of
+// rec_out / rec_tmp pass 0 does not write, and that buffer is free again when
+// pass 1 overwrites it, so rec_tmp is needed for every number of passes and
+// no third record buffer for any; keys_tmp from two passes on, as above.
+void onesweep_sort_csr_launch(void* work, const int* row_ptr,
+                              const int* keys_in, const float* vals, int B,
+                              int* keys_out, int* keys_tmp, int* rec_out,
+                              int* rec_tmp, int n, int end_bit, int* status,
+                              hipStream_t stream) {
+  if (n <= 0 || B <= 0) return;
+  const int passes = os_passes(end_bit);
+  const int tile = kOsThreads * kOsItems;
+  const int tiles = (n + tile - 1) / tile;
+  const unsigned keymask = (1u << end_bit) - 1u;
+  unsigned* ghist = (unsigned*)work;
+  hipLaunchKernelGGL(onesweep_zero_kernel, dim3(1), dim3(kOsCtrlWords / 4), 0,
+                     stream, (uint4*)work);
+  const int wpb = kOsHistMaxThreads / 64;
+  const int hist_blocks = std::min(
+      kOsHistRecMaxBlocks, (B + wpb * kOsHistRows - 1) / (wpb * kOsHistRows));
+  int* rec_csr = (passes & 1) ? rec_tmp : rec_out;
+  hipLaunchKernelGGL(onesweep_hist_rec_kernel, dim3(hist_blocks),
+                     dim3(kOsHistMaxThreads), 0, stream, row_ptr, keys_in, vals,
+                     (int2*)rec_csr, B, n, passes, keymask, ghist,
+                     (uint4*)(ghist + kOsCtrlWords),
+                     (long)(passes * (size_t)tiles * kOsRadix / 4));
+  os_scatter_passes(ghist, keys_in, keys_out, keys_tmp,
+                    (const SortRec*)rec_csr, (SortRec*)rec_out,
+                    (SortRec*)rec_tmp, n, passes, tiles, keymask, status,
+                    stream);
 }
 
 // ---------------------------------------------------------------------------
