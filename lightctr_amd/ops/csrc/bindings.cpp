@@ -39,6 +39,49 @@ void check_embed_k(int64_t K) {
       "latent width K must be one of 4, 8, 16, 32, 64, got ", K);
 }
 
+// The FM launchers dispatch K over the same set and abort() likewise: V is
+// [F, K] fp32 with K in it. Returns K.
+int check_fm_v(const at::Tensor& V) {
+  check_cuda_f32(V, "V");
+  CHK(V.dim() == 2, "V must be [F, K]");
+  check_embed_k(V.size(1));
+  return (int)V.size(1);
+}
+
+// fp32 / int32 device array of exactly n elements
+void check_f32_n(const at::Tensor& t, int64_t n, const char* name) {
+  check_cuda_f32(t, name);
+  CHK(t.numel() == n, name, " must hold ", n, " elements, got ", t.numel());
+}
+
+void check_i32_n(const at::Tensor& t, int64_t n, const char* name) {
+  check_cuda_i32(t, name);
+  CHK(t.numel() == n, name, " must hold ", n, " elements, got ", t.numel());
+}
+
+// touched bitmap: one 64-bit word per 64 features
+void check_touched(const at::Tensor& touched, int64_t F) {
+  CHK(touched.is_cuda(), "touched must be on GPU");
+  CHK(touched.scalar_type() == at::kLong ||
+          touched.scalar_type() == at::kUInt64,
+      "touched must be 64-bit");
+  CHK(touched.is_contiguous(), "touched must be contiguous");
+  CHK(touched.numel() >= (F + 63) / 64, "touched must hold ", (F + 63) / 64,
+      " words for ", F, " features, got ", touched.numel());
+}
+
+// CSR batch of the FM row kernels: B + 1 offsets, one value per entry.
+// Returns B.
+int check_fm_csr(const at::Tensor& row_ptr, const at::Tensor& fids,
+                 const at::Tensor& vals) {
+  check_cuda_i32(row_ptr, "row_ptr");
+  check_cuda_i32(fids, "fids");
+  check_cuda_f32(vals, "vals");
+  CHK(row_ptr.numel() >= 1, "row_ptr must hold B + 1 offsets");
+  CHK(vals.numel() == fids.numel(), "vals must have one value per entry");
+  return (int)row_ptr.numel() - 1;
+}
+
 // the FFM launchers dispatch K over the same set and abort() likewise
 void check_ffm_v(const at::Tensor& V) {
   CHK(V.dim() == 3, "V must be [F, nfields, K]");
@@ -73,19 +116,17 @@ at::Tensor perm32(const at::Tensor& perm) {
 std::vector<at::Tensor> fm_forward(at::Tensor row_ptr, at::Tensor fids,
                                    at::Tensor vals, at::Tensor W,
                                    at::Tensor V) {
-  check_cuda_i32(row_ptr, "row_ptr");
-  check_cuda_i32(fids, "fids");
-  check_cuda_f32(vals, "vals");
-  check_cuda_f32(W, "W");
-  check_cuda_f32(V, "V");
-  const int B = (int)row_ptr.numel() - 1;
-  const int K = (int)V.size(1);
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_fm_v(V);
+  check_f32_n(W, V.size(0), "W");
   auto pred = at::empty({B}, W.options());
   auto sumVX = at::empty({B, K}, W.options());
+  if (B == 0) return {pred, sumVX};  // nothing is launched for an empty batch
   lightctr::fm_forward_launch(row_ptr.data_ptr<int>(), fids.data_ptr<int>(),
                               vals.data_ptr<float>(), W.data_ptr<float>(),
                               V.data_ptr<float>(), pred.data_ptr<float>(),
                               sumVX.data_ptr<float>(), B, K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return {pred, sumVX};
 }
 
@@ -108,16 +149,11 @@ std::vector<at::Tensor> fm_forward_train(at::Tensor row_ptr, at::Tensor fids,
                                          at::Tensor V, at::Tensor label,
                                          double scale,
                                          c10::optional<at::Tensor> reset) {
-  check_cuda_i32(row_ptr, "row_ptr");
-  check_cuda_i32(fids, "fids");
-  check_cuda_f32(vals, "vals");
-  check_cuda_f32(W, "W");
-  check_cuda_f32(V, "V");
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_fm_v(V);
+  check_f32_n(W, V.size(0), "W");
   check_cuda_f32(label, "label");
-  const int B = (int)row_ptr.numel() - 1;
-  const int K = (int)V.size(1);
   const long nnz = fids.numel();
-  CHK(vals.numel() == nnz, "vals must have one value per entry");
   CHK(label.numel() == B, "label must have one value per row");
   auto loss = at::empty({B}, W.options());
   auto dpred = at::empty({B}, W.options());
@@ -130,12 +166,14 @@ std::vector<at::Tensor> fm_forward_train(at::Tensor row_ptr, at::Tensor fids,
     reset_ptr = reset->data_ptr<int>();
     if (B <= 0) reset->zero_();  // nothing is launched for an empty batch
   }
+  if (B == 0) return {loss, dpred, sumVX, rec};
   lightctr::fm_forward_train_launch(
       row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
       W.data_ptr<float>(), V.data_ptr<float>(), label.data_ptr<float>(),
       (float)scale, loss.data_ptr<float>(), dpred.data_ptr<float>(),
       sumVX.data_ptr<float>(), rec.data_ptr<int>(), B, K, reset_ptr,
       cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return {loss, dpred, sumVX, rec};
 }
 
@@ -144,45 +182,46 @@ std::vector<at::Tensor> logloss_grad(at::Tensor pred, at::Tensor label,
   check_cuda_f32(pred, "pred");
   check_cuda_f32(label, "label");
   const int B = (int)pred.numel();
+  CHK(label.numel() == B, "label must have one value per row");
   auto loss = at::empty_like(pred);
   auto dpred = at::empty_like(pred);
+  if (B == 0) return {loss, dpred};
   lightctr::logloss_grad_launch(pred.data_ptr<float>(),
                                 label.data_ptr<float>(),
                                 loss.data_ptr<float>(), dpred.data_ptr<float>(),
                                 (float)scale, B, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return {loss, dpred};
 }
 
 void fm_backward(at::Tensor row_ptr, at::Tensor fids, at::Tensor vals,
                  at::Tensor V, at::Tensor sumVX, at::Tensor dpred,
                  at::Tensor gradW, at::Tensor gradV, at::Tensor touched) {
-  check_cuda_i32(row_ptr, "row_ptr");
-  check_cuda_i32(fids, "fids");
-  check_cuda_f32(vals, "vals");
-  check_cuda_f32(V, "V");
-  check_cuda_f32(sumVX, "sumVX");
-  check_cuda_f32(dpred, "dpred");
-  check_cuda_f32(gradW, "gradW");
-  check_cuda_f32(gradV, "gradV");
-  CHK(touched.scalar_type() == at::kLong || touched.scalar_type() == at::kUInt64,
-      "touched must be 64-bit");
-  const int B = (int)row_ptr.numel() - 1;
-  const int K = (int)V.size(1);
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_fm_v(V);
+  const int64_t F = V.size(0);
+  check_f32_n(sumVX, (int64_t)B * K, "sumVX");
+  check_f32_n(dpred, B, "dpred");
+  check_f32_n(gradW, F, "gradW");
+  check_f32_n(gradV, F * K, "gradV");
+  check_touched(touched, F);
+  if (B == 0) return;
   lightctr::fm_backward_launch(
       row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
       V.data_ptr<float>(), sumVX.data_ptr<float>(), dpred.data_ptr<float>(),
       gradW.data_ptr<float>(), gradV.data_ptr<float>(),
       (unsigned long long*)touched.data_ptr(), B, K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 std::vector<at::Tensor> fm_backward_emit(at::Tensor row_ptr, at::Tensor fids,
                                          at::Tensor vals, at::Tensor V,
                                          at::Tensor sumVX, at::Tensor dpred,
                                          c10::optional<at::Tensor> pos) {
-  check_cuda_i32(row_ptr, "row_ptr");
-  check_cuda_i32(fids, "fids");
-  const int B = (int)row_ptr.numel() - 1;
-  const int K = (int)V.size(1);
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_fm_v(V);
+  check_f32_n(sumVX, (int64_t)B * K, "sumVX");
+  check_f32_n(dpred, B, "dpred");
   const auto nnz = fids.numel();
   auto gw = at::empty({nnz}, V.options());
   auto gv = at::empty({nnz, K}, V.options());
@@ -192,11 +231,13 @@ std::vector<at::Tensor> fm_backward_emit(at::Tensor row_ptr, at::Tensor fids,
     CHK(pos->numel() == nnz, "pos must have one slot per entry");
     pos_ptr = pos->data_ptr<int>();
   }
+  if (B == 0 || nnz == 0) return {gw, gv};
   lightctr::fm_backward_emit_launch(
       row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
       V.data_ptr<float>(), sumVX.data_ptr<float>(), dpred.data_ptr<float>(),
       gw.data_ptr<float>(), gv.data_ptr<float>(), B, K, pos_ptr,
       cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
   return {gw, gv};
 }
 
@@ -213,17 +254,43 @@ at::Tensor inv_perm_i32(at::Tensor perm_in) {
   return inv;
 }
 
+// What both sorted applies read: the sorted stream, the per-entry gradients
+// behind it, the slabs and the bitmap. Returns K (from gradV [F, K]);
+// perm_i holds the int32 permutation when one is given.
+int check_sorted_apply(const at::Tensor& sorted_fids,
+                       const c10::optional<at::Tensor>& perm,
+                       const at::Tensor& gw, const at::Tensor& gv,
+                       const at::Tensor& gradW, const at::Tensor& gradV,
+                       const at::Tensor& touched, at::Tensor& perm_i) {
+  check_cuda_i32(sorted_fids, "sorted_fids");
+  check_cuda_f32(gradV, "gradV");
+  CHK(gradV.dim() == 2, "gradV must be [F, K]");
+  check_embed_k(gradV.size(1));
+  const int64_t nnz = sorted_fids.numel();
+  const int64_t F = gradV.size(0), K = gradV.size(1);
+  check_f32_n(gradW, F, "gradW");
+  check_f32_n(gw, nnz, "gw");
+  check_f32_n(gv, nnz * K, "gv");
+  check_touched(touched, F);
+  if (perm.has_value()) {
+    CHK(perm->is_cuda(), "perm must be on GPU");
+    CHK(perm->numel() == nnz, "perm must have one slot per entry");
+    perm_i = perm32(*perm).contiguous();
+  }
+  return (int)K;
+}
+
 void fm_sorted_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
                      at::Tensor gw, at::Tensor gv, at::Tensor gradW,
                      at::Tensor gradV, at::Tensor touched, int64_t chunk) {
-  check_cuda_i32(sorted_fids, "sorted_fids");
-  const int* perm_ptr = nullptr;
   at::Tensor perm_i;
-  if (perm.has_value()) {
-    perm_i = perm32(*perm).contiguous();
-    perm_ptr = perm_i.data_ptr<int>();
-  }
-  const int K = (int)gradV.size(1);
+  const int K = check_sorted_apply(sorted_fids, perm, gw, gv, gradW, gradV,
+                                   touched, perm_i);
+  CHK(chunk >= -4 && chunk <= std::numeric_limits<int>::max(),
+      "chunk must be positive or one of 0 (default walk), -1, -2 (segmented "
+      "scans), -3, -4 (walk variants), got ", chunk);
+  const int* perm_ptr = perm.has_value() ? perm_i.data_ptr<int>() : nullptr;
+  if (sorted_fids.numel() == 0) return;
   lightctr::fm_sorted_apply_launch(
       sorted_fids.data_ptr<int>(), perm_ptr,
       gw.data_ptr<float>(), gv.data_ptr<float>(), gradW.data_ptr<float>(),
@@ -231,6 +298,7 @@ void fm_sorted_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
       (int)sorted_fids.numel(), K, 0, nullptr, nullptr, nullptr, nullptr,
       nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, (int)chunk,
       cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 // Fused variant: interior feature segments get their optimizer update
@@ -245,17 +313,26 @@ void fm_sorted_apply_fused(at::Tensor sorted_fids,
                            c10::optional<at::Tensor> zV, int64_t opt_mode,
                            double p0, double p1, double p2, double p3,
                            double v_lr, double v_eps, double v_l2) {
-  check_cuda_i32(sorted_fids, "sorted_fids");
-  const int* perm_ptr = nullptr;
   at::Tensor perm_i;
-  if (perm.has_value()) {
-    perm_i = perm32(*perm).contiguous();
-    perm_ptr = perm_i.data_ptr<int>();
-  }
+  const int K = check_sorted_apply(sorted_fids, perm, gw, gv, gradW, gradV,
+                                   touched, perm_i);
+  const int* perm_ptr = perm.has_value() ? perm_i.data_ptr<int>() : nullptr;
   CHK(opt_mode == 1 || opt_mode == 2 || opt_mode == 3,
       "opt_mode 1=adagrad 2=ftrl 3=ftrlW+adagradV");
-  if (opt_mode == 3) CHK(zW.has_value(), "opt_mode 3 needs zW");
-  const int K = (int)gradV.size(1);
+  const int64_t F = gradV.size(0);
+  CHK(check_fm_v(V) == K && V.size(0) == F, "V must match gradV");
+  check_f32_n(W, F, "W");
+  check_f32_n(nW, F, "nW");
+  check_f32_n(nV, F * K, "nV");
+  if (opt_mode != 1) {
+    CHK(zW.has_value(), "FTRL needs zW");
+    check_f32_n(*zW, F, "zW");
+  }
+  if (opt_mode == 2) {
+    CHK(zV.has_value(), "FTRL on V needs zV");
+    check_f32_n(*zV, F * K, "zV");
+  }
+  if (sorted_fids.numel() == 0) return;
   lightctr::fm_sorted_apply_launch(
       sorted_fids.data_ptr<int>(), perm_ptr,
       gw.data_ptr<float>(), gv.data_ptr<float>(), gradW.data_ptr<float>(),
@@ -267,6 +344,7 @@ void fm_sorted_apply_fused(at::Tensor sorted_fids,
       zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0,
       (float)p1, (float)p2, (float)p3, (float)v_lr, (float)v_eps,
       (float)v_l2, 384, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 // Work list of the segment backward: (piece_start int32 [nnz], n_pieces
@@ -320,7 +398,7 @@ void check_segment_state(const at::Tensor& sorted_fids,
   check_cuda_f32(V, "V");
   check_cuda_f32(nW, "nW");
   check_cuda_f32(nV, "nV");
-  const int K = (int)V.size(1);
+  const int K = check_fm_v(V);
   CHK(spill_count.numel() >= 1, "counters");
   CHK(gradV.numel() == V.numel() && gradW.numel() == W.numel() &&
           nV.numel() == V.numel() && nW.numel() == W.numel() &&
@@ -401,6 +479,7 @@ void fm_segment_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
       zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
       (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
       num_cus, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 // Segment backward from the sorted records of fm_forward_train: each entry's
@@ -440,6 +519,7 @@ void fm_segment_apply_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
       zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
       (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
       num_cus, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 // Tile-local segment backward from the sorted records: what
@@ -479,6 +559,7 @@ void fm_segment_tile_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
       zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
       (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
       cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 // ---- FFM ----
@@ -998,30 +1079,55 @@ void fm_adagrad_apply(at::Tensor uniq, at::Tensor count, at::Tensor W,
                       double eps, double l2) {
   check_cuda_i32(uniq, "uniq");
   check_cuda_i32(count, "count");
-  const int K = (int)V.size(1);
+  CHK(count.numel() >= 1, "count must hold one int");
+  const int K = check_fm_v(V);
+  const int64_t F = V.size(0);
+  check_f32_n(W, F, "W");
+  check_f32_n(nW, F, "nW");
+  check_f32_n(nV, F * K, "nV");
+  check_f32_n(gradW, F, "gradW");
+  check_f32_n(gradV, F * K, "gradV");
+  if (uniq.numel() == 0) return;  // a grid of 0 blocks is a launch error
   lightctr::fm_adagrad_apply_launch(
       uniq.data_ptr<int>(), count.data_ptr<int>(), W.data_ptr<float>(),
       V.data_ptr<float>(), nW.data_ptr<float>(), nV.data_ptr<float>(),
       gradW.data_ptr<float>(), gradV.data_ptr<float>(), (float)lr, (float)eps,
       (float)l2, (int)uniq.numel(), K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 void fm_ftrl_apply(at::Tensor uniq, at::Tensor count, at::Tensor W,
-                   at::Tensor V, at::Tensor zW, at::Tensor nW, at::Tensor zV,
-                   at::Tensor nV, at::Tensor gradW, at::Tensor gradV,
+                   at::Tensor V, at::Tensor zW, at::Tensor nW,
+                   c10::optional<at::Tensor> zV, at::Tensor nV, at::Tensor gradW, at::Tensor gradV,
                    double alpha, double beta, double l1, double l2,
                    int64_t v_adagrad, double v_lr, double v_eps,
                    double v_l2) {
   check_cuda_i32(uniq, "uniq");
   check_cuda_i32(count, "count");
-  const int K = (int)V.size(1);
+  CHK(count.numel() >= 1, "count must hold one int");
+  const int K = check_fm_v(V);
+  const int64_t F = V.size(0);
+  check_f32_n(W, F, "W");
+  check_f32_n(zW, F, "zW");
+  check_f32_n(nW, F, "nW");
+  check_f32_n(nV, F * K, "nV");
+  check_f32_n(gradW, F, "gradW");
+  check_f32_n(gradV, F * K, "gradV");
+  float* zV_ptr = nullptr;  // Adagrad on V keeps no z
+  if (zV.has_value()) {
+    check_f32_n(*zV, F * K, "zV");
+    zV_ptr = zV->data_ptr<float>();
+  }
+  CHK(v_adagrad != 0 || zV_ptr != nullptr, "FTRL on V needs zV");
+  if (uniq.numel() == 0) return;  // a grid of 0 blocks is a launch error
   lightctr::fm_ftrl_apply_launch(
       uniq.data_ptr<int>(), count.data_ptr<int>(), W.data_ptr<float>(),
       V.data_ptr<float>(), zW.data_ptr<float>(), nW.data_ptr<float>(),
-      zV.data_ptr<float>(), nV.data_ptr<float>(), gradW.data_ptr<float>(),
+      zV_ptr, nV.data_ptr<float>(), gradW.data_ptr<float>(),
       gradV.data_ptr<float>(), (float)alpha, (float)beta, (float)l1,
       (float)l2, (int)uniq.numel(), K, (int)v_adagrad, (float)v_lr,
       (float)v_eps, (float)v_l2, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
 
 // ---- dense NN ops ----
@@ -1403,11 +1509,10 @@ std::vector<at::Tensor> fm_forward_train_sorted(
     c10::optional<at::Tensor> reset, c10::optional<at::Tensor> status,
     bool overlap) {
   check_csr_sort(row_ptr, fids, vals, end_bit, status);
-  check_cuda_f32(W, "W");
-  check_cuda_f32(V, "V");
+  const int K = check_fm_v(V);
+  check_f32_n(W, V.size(0), "W");
   check_cuda_f32(label, "label");
   const int B = (int)row_ptr.numel() - 1;
-  const int K = (int)V.size(1);
   const long nnz = fids.numel();
   CHK(label.numel() == B, "label must have one value per row");
   int* reset_ptr = nullptr;
