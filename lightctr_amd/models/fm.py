@@ -123,9 +123,11 @@ class FMModel:
         self.sort_status = torch.zeros(1, dtype=torch.int32,
                                        device=self.device)
         # front half of "segment" / "segment_list" with the onesweep sort.
-        # True: the sort makes the records itself (row-walking histogram)
-        # and runs on a pool stream beside a forward that writes none; the
-        # two join in front of the reduce. "serial": the same launches in
+        # True: the sort makes the records itself (its first scatter pass
+        # reads fids and vals and looks each entry's row up in row_ptr; no
+        # record exists in batch order) and runs on a pool stream beside a
+        # forward that writes none; the two join in front of the reduce.
+        # "serial": the same launches in
         # sequence on one stream. False: the forward writes the records and
         # the sort follows it (the earlier sequence). All three hand the
         # reduce a bit-identical sorted stream; measurements in

@@ -1461,8 +1461,10 @@ CsrSortBuffers alloc_csr_sort(const at::Tensor& fids, int64_t end_bit,
   const unsigned long bytes =
       lightctr::onesweep_sort_work_bytes((int)n, (int)end_bit);
   b.work = at::empty({(long)bytes}, fids.options().dtype(at::kByte));
-  b.rec_tmp = at::empty({n, 2}, fids.options());
-  if (end_bit > 8) b.keys_tmp = at::empty_like(fids);
+  if (end_bit > 8) {  // the ping-pong pair, from two passes on
+    b.keys_tmp = at::empty_like(fids);
+    b.rec_tmp = at::empty({n, 2}, fids.options());
+  }
   return b;
 }
 
@@ -1474,12 +1476,14 @@ void launch_csr_sort(const CsrSortBuffers& b, const at::Tensor& row_ptr,
       vals.data_ptr<float>(), (int)row_ptr.numel() - 1,
       b.sorted.data_ptr<int>(),
       end_bit > 8 ? b.keys_tmp.data_ptr<int>() : nullptr,
-      b.sorted_rec.data_ptr<int>(), b.rec_tmp.data_ptr<int>(),
-      (int)fids.numel(), (int)end_bit, b.status.data_ptr<int>(), stream);
+      b.sorted_rec.data_ptr<int>(),
+      end_bit > 8 ? b.rec_tmp.data_ptr<int>() : nullptr, (int)fids.numel(),
+      (int)end_bit, b.status.data_ptr<int>(), stream);
 }
 
 // onesweep_sort_rec(fids, fm_records(row_ptr, vals)) without the records'
-// own launch: the histogram kernel walks the rows and writes them.
+// own launch and without the records in CSR order: the first scatter pass
+// reads fids and vals and finds each entry's row in row_ptr itself.
 std::vector<at::Tensor> onesweep_sort_csr(at::Tensor row_ptr, at::Tensor fids,
                                           at::Tensor vals, int64_t end_bit,
                                           c10::optional<at::Tensor> status) {
@@ -1491,7 +1495,9 @@ std::vector<at::Tensor> onesweep_sort_csr(at::Tensor row_ptr, at::Tensor fids,
 }
 
 // Front half of the segment-mode training step: the training forward (no
-// records) and the record sort of the batch. The sort reads only the batch,
+// records) and the record sort of the batch (keys-only histogram; the first
+// scatter pass reads fids and vals and finds the rows, so no record is written
+// in batch order). The sort reads only the batch,
 // so with overlap it runs on a pool stream beside the forward: fork by an
 // event on the current stream, join by an event on the pool stream, no sync
 // and no host read, so a stream capture records the two as parallel branches
@@ -2286,7 +2292,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("row_ptr"), py::arg("vals"));
   m.def("onesweep_sort_csr", &onesweep_sort_csr,
         "onesweep sort of a CSR batch's (fid, record) stream, the records "
-        "made by the histogram kernel -> (sorted, sorted_rec)",
+        "made by the first scatter pass -> (sorted, sorted_rec)",
         py::arg("row_ptr"), py::arg("fids"), py::arg("vals"),
         py::arg("end_bit"), py::arg("status") = py::none());
   m.def("fm_forward_train_sorted", &fm_forward_train_sorted,

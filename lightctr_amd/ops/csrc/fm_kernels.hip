@@ -130,9 +130,9 @@ __device__ __forceinline__ void logloss_grad_row(float z, float y, float scale,
 // lane of the feature group that has just loaded vals[j]): the segment
 // backward sorts these records by fid and recomputes each entry's gradient
 // from them, so no per-entry gradient buffer is ever written. The records
-// are pure batch data: fm_records_kernel and the row-walking histogram of
-// sort_kernels.hip write the same ones without the model, which lets the
-// sort run beside a forward that has REC off.
+// are pure batch data: fm_records_kernel writes the same ones without the
+// model and the CSR-fed sort of sort_kernels.hip makes them in registers in
+// its first pass, which lets the sort run beside a forward that has REC off.
 // Returns the row's pred (valid in every lane).
 template <int K, bool REC>
 __device__ __forceinline__ float fm_forward_row(

@@ -352,10 +352,10 @@ void onesweep_sort_rec_launch(void* work, const int* keys_in, int* keys_out,
                               int* rec_tmp, int n, int end_bit, int* status,
                               ihipStream_t* stream);
 // the same sort of a CSR batch's (fid, {row, bits of x}) stream, n =
-// row_ptr[B]: the histogram kernel makes the records, so nothing of it
-// depends on the model. rec_tmp is needed for every end_bit here, keys_tmp
-// from two passes on. Kernels only: a one-block kernel zeroes the control
-// block in place of the memset
+// row_ptr[B]: the first scatter pass reads keys_in and vals and finds each
+// entry's row in row_ptr, so no record exists in CSR order and nothing of the
+// sort depends on the model. keys_tmp / rec_tmp from two passes on. Kernels
+// only: a one-block kernel zeroes the control block in place of the memset
 void onesweep_sort_csr_launch(void* work, const int* row_ptr,
                               const int* keys_in, const float* vals, int B,
                               int* keys_out, int* keys_tmp, int* rec_out,

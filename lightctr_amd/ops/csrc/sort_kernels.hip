@@ -125,6 +125,12 @@ void radix_sort_pairs_rec_launch(void* temp, size_t temp_bytes,
 //     consecutive lanes on consecutive addresses. The reorder buffers reuse
 //     the ranking tables' bytes: 50 KB per 4096-entry tile, 3 blocks per CU,
 //     so the flagship's 624 tiles are resident at once.
+//
+// Fed by a CSR batch (onesweep_sort_csr_launch), pass 0 is the CSR
+// instantiation of the scatter kernel: it reads fids and vals, 8 bytes an
+// entry, and makes each record {row, bits of x} in registers, the row looked
+// up in row_ptr. The records never exist in batch order and the histogram
+// kernel is the keys-only one (profiles/r8_01_fm_csr_scatter.txt).
 // ---------------------------------------------------------------------------
 constexpr int kOsRadix = 256;
 constexpr int kOsMaxPasses = 4;
@@ -137,7 +143,6 @@ constexpr unsigned kOsPrefix = 2u << 30;
 constexpr unsigned kOsSpinLimit = 1u << 20;
 constexpr int kOsHistMaxThreads = 1024;
 constexpr int kOsHistMaxBlocks = 256;
-constexpr int kOsHistRecMaxBlocks = 512;
 // tile shape and look-back window: the winners of the sweep in
 // profiles/r6_01_fm_sort.txt (tiles of 2048 / 4096 / 8192 entries, 256- and
 // 512-thread blocks, windows of 1..64); only this shape is built
@@ -164,74 +169,6 @@ __global__ __launch_bounds__(kOsHistMaxThreads) void onesweep_hist_kernel(
 #pragma unroll
     for (int p = 0; p < kOsMaxPasses; ++p)
       if (p < passes) atomicAdd(&h[p * kOsRadix + ((k >> (8 * p)) & 255u)], 1u);
-  }
-  __syncthreads();
-  for (int i = tid; i < passes * kOsRadix; i += threads) {
-    const unsigned c = h[i];
-    if (c) atomicAdd(&ghist[i], c);
-  }
-}
-
-// Row-walking variant for a CSR batch: also writes the records the sort
-// carries, rec[j] = {row of j, bits of vals[j]} (what the FM training forward
-// writes with REC on), so the sort needs nothing from the model and no launch
-// of its own for the records. One wave per row, grid-strided over rows; a
-// wave loads the bounds of kOsHistRows rows, then their first 64 entries,
-// before it counts any (independent round trips), and walks what a longer row
-// has left afterwards. Every entry of [0, row_ptr[B]) lies in exactly one
-// row, so the histograms equal onesweep_hist_kernel's for the same keys.
-constexpr int kOsHistRows = 4;
-
-__global__ __launch_bounds__(kOsHistMaxThreads) void onesweep_hist_rec_kernel(
-    const int* __restrict__ row_ptr, const int* __restrict__ keys,
-    const float* __restrict__ vals, int2* __restrict__ rec, int B, int n,
-    int passes, unsigned keymask, unsigned* ghist, uint4* state, long state_vec4) {
-  __shared__ unsigned h[kOsMaxPasses * kOsRadix];
-  const int tid = threadIdx.x, threads = blockDim.x;
-  for (int i = tid; i < passes * kOsRadix; i += threads) h[i] = 0;
-  const long gstride = (long)gridDim.x * threads;
-  for (long i = (long)blockIdx.x * threads + tid; i < state_vec4; i += gstride)
-    state[i] = make_uint4(0u, 0u, 0u, 0u);
-  __syncthreads();
-  const int lane = tid & 63;
-  const int wstride = (int)(gstride >> 6);
-  auto count = [&](unsigned k) {
-    k &= keymask;
-#pragma unroll
-    for (int p = 0; p < kOsMaxPasses; ++p)
-      if (p < passes) atomicAdd(&h[p * kOsRadix + ((k >> (8 * p)) & 255u)], 1u);
-  };
-  for (long row0 = ((long)blockIdx.x * threads + tid) >> 6; row0 < B;
-       row0 += (long)kOsHistRows * wstride) {
-    int row[kOsHistRows], j[kOsHistRows], end[kOsHistRows], k[kOsHistRows],
-        x[kOsHistRows];
-#pragma unroll
-    for (int u = 0; u < kOsHistRows; ++u) {
-      const long r = row0 + (long)u * wstride;
-      const bool live = r < B;
-      row[u] = (int)r;
-      // clamped to the stream: a malformed row_ptr cannot reach past it
-      j[u] = live ? max(row_ptr[r], 0) + lane : 0;
-      end[u] = live ? min(row_ptr[r + 1], n) : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < kOsHistRows; ++u) {
-      if (j[u] < end[u]) {
-        k[u] = keys[j[u]];
-        x[u] = __float_as_int(vals[j[u]]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kOsHistRows; ++u) {
-      if (j[u] < end[u]) {
-        rec[j[u]] = make_int2(row[u], x[u]);
-        count((unsigned)k[u]);
-      }
-      for (int jj = j[u] + 64; jj < end[u]; jj += 64) {
-        rec[jj] = make_int2(row[u], __float_as_int(vals[jj]));
-        count((unsigned)keys[jj]);
-      }
-    }
   }
   __syncthreads();
   for (int i = tid; i < passes * kOsRadix; i += threads) {
@@ -271,13 +208,37 @@ constexpr int os_smem_bytes() {
          48;
 }
 
-template <int THREADS, int IPT>
+// Row of a CSR entry, for the pass that reads the batch itself: row(t) is the
+// last r in [0, B-1] with row_ptr[r] <= t, which for a well-formed row_ptr is
+// the one row with row_ptr[r] <= t < row_ptr[r+1], empty rows on either side
+// included.
+//
+// One round of a wave-wide 64-ary search for it over the candidates [lo, hi]
+// (wave-uniform, lo <= hi <= B-1): lane l probes lo + (l+1) * step, the 64
+// probes cut the span into pieces of at most step - 1, and the number of
+// probes that hold picks the piece. 65536 rows take three rounds. Counting
+// the probes (not taking the first that fails) keeps the piece inside
+// [lo, hi] whatever row_ptr holds.
+__device__ __forceinline__ void os_row_search_round(
+    const int* __restrict__ row_ptr, int t, int lane, int& lo, int& hi) {
+  const int step = ((hi - lo) >> 6) + 1;
+  // hi - lo < 2^30 and lane < 64: the probe fits a long, and an int once it
+  // is known to be <= hi
+  const long p = (long)lo + (long)(lane + 1) * step;
+  const bool hit = p <= (long)hi && row_ptr[p] <= t;
+  const int c = __popcll(__ballot(hit));
+  lo += c * step;
+  hi = min(hi, lo + step - 1);
+}
+
+template <int THREADS, int IPT, bool CSR>
 __global__ __launch_bounds__(THREADS) void onesweep_scatter_kernel(
     const int* __restrict__ keys_in,
     const unsigned long long* __restrict__ rec_in, int* __restrict__ keys_out,
     unsigned long long* __restrict__ rec_out, int n, int shift,
     unsigned keymask, const unsigned* __restrict__ ghist, unsigned* ticket,
-    unsigned* state, int* status) {
+    unsigned* state, int* status, const int* __restrict__ row_ptr,
+    const float* __restrict__ vals, int B) {
   constexpr int TILE = THREADS * IPT, NW = THREADS / 64;
   static_assert(THREADS >= kOsRadix && THREADS % 64 == 0, "one thread/digit");
   constexpr int rank_bytes = NW * kOsRadix * 12 + kOsRadix * 4;
@@ -320,7 +281,68 @@ __global__ __launch_bounds__(THREADS) void onesweep_scatter_kernel(
     const int idx = wbase + i * 64;
     const bool v = idx < n;
     key[i] = v ? (unsigned)keys_in[idx] : 0u;
-    rec[i] = v ? rec_in[idx] : 0ull;
+    if constexpr (CSR)  // bits of x for now, the row joins them below
+      rec[i] = v ? (unsigned long long)__float_as_uint(vals[idx]) << 32 : 0ull;
+    else
+      rec[i] = v ? rec_in[idx] : 0ull;
+  }
+  if constexpr (CSR) {
+    // rec = {row(idx), bits of vals[idx]}, what fm_records writes. Nothing
+    // here stands in front of the loads above, and the first probes depend on
+    // the ticket alone. The wave searches for r0 = row(c0), the row of its
+    // chunk's first entry, then loads the starts of the 64 rows behind r0 with
+    // one load. If the chunk's last entry c1 lies in front of the last of
+    // them (it does unless the rows average under 8 entries), the starts go
+    // to 256 bytes of LDS that the ranking phase leaves idle, and every
+    // entry counts the starts at or in front of it by a search there: a
+    // uniform number of halvings (four at 39 entries a row), the IPT items
+    // interleaved, no further global load.
+    const int c0 = __builtin_amdgcn_readfirstlane(wbase - lane);
+    if (c0 < n) {
+      const int c1 = min(c0 + IPT * 64, n) - 1;
+      int r0 = 0, hi0 = B - 1;
+      while (hi0 > r0) os_row_search_round(row_ptr, c0, lane, r0, hi0);
+      const int wr = r0 + 1 + lane;  // rows past B-1 count as never starting
+      const int start = wr < B ? row_ptr[wr] : 0x7fffffff;
+      // rows of the window that start in the chunk: r0 + cnt <= B-1
+      const int cnt = __popcll(__ballot(start <= c1));
+      int row[IPT];
+      if (cnt < 64) {
+        static_assert(rank_bytes + NW * 256 <= main_bytes, "idle LDS");
+        int* win = (int*)(os_smem + rank_bytes) + w * 64;
+        win[lane] = start;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) row[i] = 0;
+        for (int len = cnt + 1; len > 1;) {
+          const int half = len >> 1;
+#pragma unroll
+          for (int i = 0; i < IPT; ++i)
+            if (win[row[i] + half - 1] <= wbase + i * 64) row[i] += half;
+          len -= half;
+        }
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) row[i] += r0;
+      } else {
+        // 64 rows or more start in the chunk (short and empty rows): search
+        // for r1 = row(c1) as well, then every entry searches row_ptr over
+        // [r0, r1] itself
+        int r1 = r0, hi1 = B - 1;
+        while (hi1 > r1) os_row_search_round(row_ptr, c1, lane, r1, hi1);
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) row[i] = r0;
+        for (int len = r1 - r0 + 1; len > 1;) {
+          const int half = len >> 1;
+#pragma unroll
+          for (int i = 0; i < IPT; ++i)
+            if (row_ptr[row[i] + half] <= wbase + i * 64) row[i] += half;
+          len -= half;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < IPT; ++i) rec[i] |= (unsigned long long)(unsigned)row[i];
+    }
   }
 
   // rank within the wave's chunk, row by row: the entries of a row with the
@@ -465,15 +487,16 @@ __global__ __launch_bounds__(THREADS) void onesweep_scatter_kernel(
   }
 }
 
-template <int THREADS, int IPT>
+template <int THREADS, int IPT, bool CSR>
 void os_scatter_launch(int tiles, const int* keys_in, const SortRec* rec_in,
                        int* keys_out, SortRec* rec_out, int n, int shift,
                        unsigned keymask, const unsigned* ghist,
                        unsigned* ticket, unsigned* state, int* status,
+                       const int* row_ptr, const float* vals, int B,
                        hipStream_t stream) {
   constexpr int smem = os_smem_bytes<THREADS, IPT>();
   static_assert(smem <= 160 * 1024, "tile does not fit the LDS");
-  auto kernel = onesweep_scatter_kernel<THREADS, IPT>;
+  auto kernel = onesweep_scatter_kernel<THREADS, IPT, CSR>;
   if (smem > 64 * 1024) {
     static const hipError_t raised = hipFuncSetAttribute(
         (const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
@@ -481,7 +504,7 @@ void os_scatter_launch(int tiles, const int* keys_in, const SortRec* rec_in,
   }
   hipLaunchKernelGGL(kernel, dim3(tiles), dim3(THREADS), smem, stream, keys_in,
                      rec_in, keys_out, rec_out, n, shift, keymask, ghist,
-                     ticket, state, status);
+                     ticket, state, status, row_ptr, vals, B);
 }
 
 int onesweep_sort_tile() { return kOsThreads * kOsItems; }
@@ -496,14 +519,28 @@ size_t onesweep_sort_work_bytes(int n, int end_bit) {
          (size_t)os_passes(end_bit) * tiles * kOsRadix * 4;
 }
 
-// The scatter passes shared by both front ends. The passes ping-pong so that
-// the last one lands in the output pair.
-static void os_scatter_passes(unsigned* ghist, const int* keys_in,
-                              int* keys_out, int* keys_tmp,
-                              const SortRec* rec_in, SortRec* rec_out,
-                              SortRec* rec_tmp, int n, int passes, int tiles,
-                              unsigned keymask, int* status,
-                              hipStream_t stream) {
+// The histogram kernel and the scatter passes shared by both front ends, behind
+// whatever zeroed the control block. The passes ping-pong so that the last one
+// lands in the output pair. With a row_ptr, pass 0 takes its records from the
+// CSR batch (rec_in is not read); every later pass reads what the one before
+// it wrote.
+static void os_hist_and_passes(unsigned* ghist, const int* keys_in,
+                               int* keys_out, int* keys_tmp,
+                               const SortRec* rec_in, SortRec* rec_out,
+                               SortRec* rec_tmp, int n, int end_bit,
+                               int* status, const int* row_ptr,
+                               const float* vals, int B, hipStream_t stream) {
+  const int passes = os_passes(end_bit);
+  const int tile = kOsThreads * kOsItems;
+  const int tiles = (n + tile - 1) / tile;
+  const unsigned keymask = (1u << end_bit) - 1u;
+  const int hist_blocks = std::min(
+      kOsHistMaxBlocks,
+      (n + kOsHistMaxThreads * 8 - 1) / (kOsHistMaxThreads * 8));
+  hipLaunchKernelGGL(onesweep_hist_kernel, dim3(hist_blocks),
+                     dim3(kOsHistMaxThreads), 0, stream, keys_in, n, passes,
+                     keymask, ghist, (uint4*)(ghist + kOsCtrlWords),
+                     (long)(passes * (size_t)tiles * kOsRadix / 4));
   unsigned* tickets = ghist + kOsMaxPasses * kOsRadix;
   unsigned* state = ghist + kOsCtrlWords;
   const size_t pass_words = (size_t)tiles * kOsRadix;
@@ -513,10 +550,15 @@ static void os_scatter_passes(unsigned* ghist, const int* keys_in,
     const bool to_out = ((passes - 1 - p) & 1) == 0;
     int* kdst = to_out ? keys_out : keys_tmp;
     SortRec* rdst = to_out ? rec_out : rec_tmp;
-    os_scatter_launch<kOsThreads, kOsItems>(
-        tiles, ksrc, rsrc, kdst, rdst, n, 8 * p, keymask,
-        ghist + p * kOsRadix, tickets + p, state + p * pass_words, status,
-        stream);
+    if (p == 0 && row_ptr)
+      os_scatter_launch<kOsThreads, kOsItems, true>(
+          tiles, ksrc, nullptr, kdst, rdst, n, 0, keymask, ghist, tickets,
+          state, status, row_ptr, vals, B, stream);
+    else
+      os_scatter_launch<kOsThreads, kOsItems, false>(
+          tiles, ksrc, rsrc, kdst, rdst, n, 8 * p, keymask,
+          ghist + p * kOsRadix, tickets + p, state + p * pass_words, status,
+          nullptr, nullptr, 0, stream);
     ksrc = kdst;
     rsrc = rdst;
   }
@@ -529,22 +571,11 @@ void onesweep_sort_rec_launch(void* work, const int* keys_in, int* keys_out,
                               int* rec_tmp, int n, int end_bit, int* status,
                               hipStream_t stream) {
   if (n <= 0) return;
-  const int passes = os_passes(end_bit);
-  const int tile = kOsThreads * kOsItems;
-  const int tiles = (n + tile - 1) / tile;
-  const unsigned keymask = (1u << end_bit) - 1u;
-  unsigned* ghist = (unsigned*)work;
   LCTR_CHECK_HIP(hipMemsetAsync(work, 0, (size_t)kOsCtrlWords * 4, stream));
-  const int hist_blocks = std::min(
-      kOsHistMaxBlocks,
-      (n + kOsHistMaxThreads * 8 - 1) / (kOsHistMaxThreads * 8));
-  hipLaunchKernelGGL(onesweep_hist_kernel, dim3(hist_blocks),
-                     dim3(kOsHistMaxThreads), 0, stream, keys_in, n, passes,
-                     keymask, ghist, (uint4*)(ghist + kOsCtrlWords),
-                     (long)(passes * (size_t)tiles * kOsRadix / 4));
-  os_scatter_passes(ghist, keys_in, keys_out, keys_tmp, (const SortRec*)rec_in,
-                    (SortRec*)rec_out, (SortRec*)rec_tmp, n, passes, tiles,
-                    keymask, status, stream);
+  os_hist_and_passes((unsigned*)work, keys_in, keys_out, keys_tmp,
+                     (const SortRec*)rec_in, (SortRec*)rec_out,
+                     (SortRec*)rec_tmp, n, end_bit, status, nullptr, nullptr, 0,
+                     stream);
 }
 
 // Zeroes the control block in place of the memset: run beside the forward on
@@ -555,37 +586,21 @@ __global__ __launch_bounds__(kOsCtrlWords / 4) void onesweep_zero_kernel(
   ctrl[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-// The same sort fed by a CSR batch (n = row_ptr[B] entries): the histogram
-// kernel makes the records. They are written in CSR order into whichever of
-// rec_out / rec_tmp pass 0 does not write, and that buffer is free again when
-// pass 1 overwrites it, so rec_tmp is needed for every number of passes and
-// no third record buffer for any; keys_tmp from two passes on, as above.
+// The same sort fed by a CSR batch (n = row_ptr[B] entries): pass 0 reads the
+// keys and values of the batch and makes each record {row, bits of x} in
+// registers, so no record exists in CSR order and the histogram is the
+// keys-only one. keys_tmp / rec_tmp from two passes on, as above.
 void onesweep_sort_csr_launch(void* work, const int* row_ptr,
                               const int* keys_in, const float* vals, int B,
                               int* keys_out, int* keys_tmp, int* rec_out,
                               int* rec_tmp, int n, int end_bit, int* status,
                               hipStream_t stream) {
   if (n <= 0 || B <= 0) return;
-  const int passes = os_passes(end_bit);
-  const int tile = kOsThreads * kOsItems;
-  const int tiles = (n + tile - 1) / tile;
-  const unsigned keymask = (1u << end_bit) - 1u;
-  unsigned* ghist = (unsigned*)work;
   hipLaunchKernelGGL(onesweep_zero_kernel, dim3(1), dim3(kOsCtrlWords / 4), 0,
                      stream, (uint4*)work);
-  const int wpb = kOsHistMaxThreads / 64;
-  const int hist_blocks = std::min(
-      kOsHistRecMaxBlocks, (B + wpb * kOsHistRows - 1) / (wpb * kOsHistRows));
-  int* rec_csr = (passes & 1) ? rec_tmp : rec_out;
-  hipLaunchKernelGGL(onesweep_hist_rec_kernel, dim3(hist_blocks),
-                     dim3(kOsHistMaxThreads), 0, stream, row_ptr, keys_in, vals,
-                     (int2*)rec_csr, B, n, passes, keymask, ghist,
-                     (uint4*)(ghist + kOsCtrlWords),
-                     (long)(passes * (size_t)tiles * kOsRadix / 4));
-  os_scatter_passes(ghist, keys_in, keys_out, keys_tmp,
-                    (const SortRec*)rec_csr, (SortRec*)rec_out,
-                    (SortRec*)rec_tmp, n, passes, tiles, keymask, status,
-                    stream);
+  os_hist_and_passes((unsigned*)work, keys_in, keys_out, keys_tmp, nullptr,
+                     (SortRec*)rec_out, (SortRec*)rec_tmp, n, end_bit, status,
+                     row_ptr, vals, B, stream);
 }
 
 // ---------------------------------------------------------------------------
