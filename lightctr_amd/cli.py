@@ -6,7 +6,7 @@ Makefile per-role binaries + LightCTR_* env vars) with one
 command:
 
     python -m lightctr_amd.cli train --model fm --data path.csv --epochs 5
-    python -m lightctr_amd.cli train --model ffm|nfm|widedeep|gbm ...
+    python -m lightctr_amd.cli train --model ffm|nfm|widedeep|deepfm|gbm ...
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
     python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
         --data dense.csv ...      (dense rows; served by the compiled forest)
@@ -48,7 +48,7 @@ def _load_data(args):
 
 def cmd_train(args) -> int:
     dev = _device(args)
-    if args.model not in ("fm", "ffm", "nfm", "widedeep", "lr"):
+    if args.model not in ("fm", "ffm", "nfm", "widedeep", "deepfm", "lr"):
         # the rest of the zoo reads dense / text data, not libffm
         return _train_other(args, dev)
     ds = _load_data(args)
@@ -85,6 +85,16 @@ def cmd_train(args) -> int:
                                                lr=args.lr),
                              device=dev, batch_size=args.batch,
                              epochs=args.epochs)
+    elif args.model == "deepfm":
+        from .models.deepfm import DeepFMHyper, DeepFMTrainer
+
+        tr = DeepFMTrainer(ds, DeepFMHyper(num_features=F,
+                                           num_fields=ds.num_fields,
+                                           k=args.k,
+                                           optimizer=args.optimizer,
+                                           lr=args.lr),
+                           device=dev, batch_size=args.batch,
+                           epochs=args.epochs)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRTrainer
 
@@ -408,6 +418,14 @@ def cmd_predict(args) -> int:
                                             k=args.k,
                                             optimizer=args.optimizer),
                               device=dev)
+    elif args.model == "deepfm":
+        from .models.deepfm import DeepFMHyper, DeepFMModel
+
+        model = DeepFMModel(DeepFMHyper(num_features=F,
+                                        num_fields=ds.num_fields,
+                                        k=args.k,
+                                        optimizer=args.optimizer),
+                            device=dev)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRModel
 

@@ -2,6 +2,7 @@ from .fm import FMModel, FMTrainer, FMHyper
 from .ffm import FFMModel, FFMTrainer, FFMHyper
 from .nfm import NFMModel, NFMTrainer, NFMHyper
 from .wide_deep import WideDeepModel, WideDeepTrainer, WideDeepHyper
+from .deepfm import DeepFMModel, DeepFMTrainer, DeepFMHyper
 from .mlp import MLP, DenseLayer
 from .gbm import GBMModel, GBMHyper
 from .gmm import GMMModel, GMMHyper
@@ -18,6 +19,7 @@ __all__ = [
     "FFMModel", "FFMTrainer", "FFMHyper",
     "NFMModel", "NFMTrainer", "NFMHyper",
     "WideDeepModel", "WideDeepTrainer", "WideDeepHyper",
+    "DeepFMModel", "DeepFMTrainer", "DeepFMHyper",
     "MLP", "DenseLayer",
     "GBMModel", "GBMHyper",
     "GMMModel", "GMMHyper",

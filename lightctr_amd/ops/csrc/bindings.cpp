@@ -1734,6 +1734,69 @@ std::vector<at::Tensor> nfm_backward_emit(at::Tensor row_ptr, at::Tensor fids,
   return {gw, gv};
 }
 
+// ---- DeepFM ----
+
+// E is [F, K] fp32 with K in the dispatch set. Returns K.
+int check_deepfm_e(const at::Tensor& E) {
+  check_cuda_f32(E, "E");
+  CHK(E.dim() == 2, "E must be [F, K]");
+  check_embed_k(E.size(1));
+  return (int)E.size(1);
+}
+
+// FM score (wide + pair term), sumVX and the bf16 concat [B, nf*K] of one
+// shared table in one pass over the batch: fm_forward + embed_gather.
+std::vector<at::Tensor> deepfm_forward(at::Tensor row_ptr, at::Tensor fids,
+                                       at::Tensor vals, at::Tensor W,
+                                       at::Tensor E, int64_t nf) {
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_deepfm_e(E);
+  check_f32_n(W, E.size(0), "W");
+  CHK(nf >= 1, "nf must be >= 1");
+  CHK(nf * K <= std::numeric_limits<int>::max(), "nf * K must fit an int");
+  auto fm = at::empty({B}, E.options());
+  auto sumVX = at::empty({B, K}, E.options());
+  auto deep_in = at::empty({B, nf * K}, E.options().dtype(at::kBFloat16));
+  if (B == 0) return {fm, sumVX, deep_in};  // nothing is launched
+  lightctr::deepfm_forward_launch(
+      row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
+      W.data_ptr<float>(), E.data_ptr<float>(), deep_in.data_ptr(),
+      sumVX.data_ptr<float>(), fm.data_ptr<float>(), (int)nf, B, K,
+      cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {fm, sumVX, deep_in};
+}
+
+// Per-entry gradients of both uses of E in one [nnz, K] buffer:
+// gv = (dDeep + dpred (sumVX - E x)) x, gw = dpred x.
+std::vector<at::Tensor> deepfm_backward_emit(
+    at::Tensor row_ptr, at::Tensor fids, at::Tensor vals, at::Tensor E,
+    at::Tensor sumVX, at::Tensor dDeep, at::Tensor dpred, int64_t nf) {
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_deepfm_e(E);
+  CHK(nf >= 1, "nf must be >= 1");
+  CHK(nf * K <= std::numeric_limits<int>::max(), "nf * K must fit an int");
+  check_cuda_f32(sumVX, "sumVX");
+  CHK(sumVX.dim() == 2 && sumVX.size(0) == B && sumVX.size(1) == K,
+      "sumVX must be [B, K]");
+  check_cuda_f32(dDeep, "dDeep");
+  CHK(dDeep.dim() == 2 && dDeep.size(0) == B && dDeep.size(1) == nf * K,
+      "dDeep must be [B, nf*K]");
+  check_cuda_f32(dpred, "dpred");
+  CHK(dpred.dim() == 1 && dpred.size(0) == B, "dpred must be [B]");
+  const auto nnz = fids.numel();
+  auto gw = at::empty({nnz}, E.options());
+  auto gv = at::empty({nnz, K}, E.options());
+  if (B == 0 || nnz == 0) return {gw, gv};
+  lightctr::deepfm_backward_emit_launch(
+      row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
+      E.data_ptr<float>(), sumVX.data_ptr<float>(), dDeep.data_ptr<float>(),
+      dpred.data_ptr<float>(), gw.data_ptr<float>(), gv.data_ptr<float>(),
+      (int)nf, B, K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {gw, gv};
+}
+
 // ---- native data loader ----
 // Fast single-pass libffm parser ("label field:fid:val" per line) —
 // native equivalent of the reference's C++ loader
@@ -2331,6 +2394,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NFM bi-interaction fwd (wide, sumVX, vec, vec_bf16)");
   m.def("nfm_backward_emit", &nfm_backward_emit,
         "NFM per-entry grads for sorted apply");
+  m.def("deepfm_forward", &deepfm_forward,
+        "DeepFM fused forward (fm, sumVX, deep_in bf16)");
+  m.def("deepfm_backward_emit", &deepfm_backward_emit,
+        "DeepFM per-entry grads (gw, gv) for sorted apply");
   m.def("bitmap_compact", &bitmap_compact, "touched bitmap -> fid list");
   m.def("wg_probe", &wg_probe, "wgrad staging/tr-read debug probe");
   m.def("gemm_bf16_variant", &gemm_bf16_variant,

@@ -302,6 +302,17 @@ void nfm_backward_emit_launch(const int* row_ptr, const int* fids,
                               const float* dwide, float* gw, float* gv, int B,
                               int K, ihipStream_t* stream);
 
+// --- deepfm_kernels.hip ---
+void deepfm_forward_launch(const int* row_ptr, const int* fids,
+                           const float* vals, const float* W, const float* E,
+                           void* out_bf, float* sumVX, float* fm, int nf,
+                           int B, int K, ihipStream_t* stream);
+void deepfm_backward_emit_launch(const int* row_ptr, const int* fids,
+                                 const float* vals, const float* E,
+                                 const float* sumVX, const float* dDeep,
+                                 const float* dpred, float* gw, float* gv,
+                                 int nf, int B, int K, ihipStream_t* stream);
+
 // --- codec_kernels.hip ---
 void quantile_encode_launch(const float* x, unsigned char* code,
                             const float* table, int levels, long n,

@@ -17,7 +17,7 @@ from lightctr_amd.data.synthetic import SyntheticCriteo
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="fm",
-                    choices=["fm", "ffm", "nfm", "widedeep"])
+                    choices=["fm", "ffm", "nfm", "widedeep", "deepfm"])
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--features", type=int, default=1 << 24)
     ap.add_argument("--reps", type=int, default=50)
@@ -44,6 +44,13 @@ def main():
 
         m = NFMModel(NFMHyper(num_features=args.features, k=16,
                               hidden=(64,)), device=dev)
+        fn = lambda: m.predict_proba(row_ptr, fids, vals)
+    elif args.model == "deepfm":
+        from lightctr_amd.models.deepfm import DeepFMHyper, DeepFMModel
+
+        m = DeepFMModel(DeepFMHyper(num_features=args.features,
+                                    num_fields=39, k=16,
+                                    hidden=(256, 128)), device=dev)
         fn = lambda: m.predict_proba(row_ptr, fids, vals)
     else:
         from lightctr_amd.models.wide_deep import (WideDeepHyper,

@@ -19,7 +19,7 @@ import torch  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="fm",
-                    choices=["fm", "ffm", "nfm", "widedeep"])
+                    choices=["fm", "ffm", "nfm", "widedeep", "deepfm"])
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--features", type=int, default=1 << 24)
@@ -52,6 +52,12 @@ def main():
 
         model = NFMModel(NFMHyper(num_features=args.features, k=args.k),
                          device=dev)
+    elif args.model == "deepfm":
+        from lightctr_amd.models.deepfm import DeepFMHyper, DeepFMModel
+
+        model = DeepFMModel(DeepFMHyper(num_features=args.features,
+                                        num_fields=39, k=args.k),
+                            device=dev)
     else:
         from lightctr_amd.models.wide_deep import (WideDeepHyper,
                                                    WideDeepModel)
