@@ -82,7 +82,9 @@ def cmd_train(args) -> int:
                                                num_fields=ds.num_fields,
                                                k=args.k,
                                                optimizer=args.optimizer,
-                                               lr=args.lr),
+                                               lr=args.lr,
+                                               layout=args.layout,
+                                               pooling=args.pooling),
                              device=dev, batch_size=args.batch,
                              epochs=args.epochs)
     elif args.model == "deepfm":
@@ -92,7 +94,9 @@ def cmd_train(args) -> int:
                                            num_fields=ds.num_fields,
                                            k=args.k,
                                            optimizer=args.optimizer,
-                                           lr=args.lr),
+                                           lr=args.lr,
+                                           layout=args.layout,
+                                           pooling=args.pooling),
                            device=dev, batch_size=args.batch,
                            epochs=args.epochs)
     elif args.model == "lr":
@@ -388,12 +392,28 @@ def _predict_dense(args, dev) -> int:
     return 0
 
 
+def _concat_setup(args, ds, dev):
+    """(checkpoint dict or None, hyper keywords) of a Wide&Deep / DeepFM
+    model to predict with. The checkpoint is read once; num_fields, layout
+    and pooling are its hyper's where it names them (a data file need not
+    carry the last field in any row), else the data's and the flags'."""
+    kw = {"num_fields": ds.num_fields, "layout": args.layout,
+          "pooling": args.pooling}
+    if not args.load:
+        return None, kw
+    ckpt = torch.load(args.load, map_location=dev, weights_only=True)
+    hyper = ckpt.get("hyper", {})
+    kw.update({k: hyper[k] for k in kw if k in hyper})
+    return ckpt, kw
+
+
 def cmd_predict(args) -> int:
     dev = _device(args)
     if args.model in ("gbm", "gbdt_lr"):
         return _predict_dense(args, dev)
     ds = _load_data(args).to(torch.device(dev))
     F = max(args.features, ds.num_features)
+    ckpt = None  # read up front by the models that size themselves from it
     if args.model == "fm":
         from .models.fm import FMHyper, FMModel
 
@@ -413,18 +433,16 @@ def cmd_predict(args) -> int:
     elif args.model == "widedeep":
         from .models.wide_deep import WideDeepHyper, WideDeepModel
 
-        model = WideDeepModel(WideDeepHyper(num_features=F,
-                                            num_fields=ds.num_fields,
-                                            k=args.k,
-                                            optimizer=args.optimizer),
+        ckpt, kw = _concat_setup(args, ds, dev)
+        model = WideDeepModel(WideDeepHyper(num_features=F, k=args.k,
+                                            optimizer=args.optimizer, **kw),
                               device=dev)
     elif args.model == "deepfm":
         from .models.deepfm import DeepFMHyper, DeepFMModel
 
-        model = DeepFMModel(DeepFMHyper(num_features=F,
-                                        num_fields=ds.num_fields,
-                                        k=args.k,
-                                        optimizer=args.optimizer),
+        ckpt, kw = _concat_setup(args, ds, dev)
+        model = DeepFMModel(DeepFMHyper(num_features=F, k=args.k,
+                                        optimizer=args.optimizer, **kw),
                             device=dev)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRModel
@@ -435,7 +453,7 @@ def cmd_predict(args) -> int:
         print(f"unknown model {args.model}", file=sys.stderr)
         return 2
     if args.load:
-        model.load(args.load)
+        model.load(ckpt if ckpt is not None else args.load)
     from .predict.predictor import BatchPredictor
 
     bp = BatchPredictor(model, batch_size=args.batch)
@@ -513,6 +531,13 @@ def build_parser():
         p.add_argument("--batch", type=int, default=256)
         p.add_argument("--lr", type=float, default=0.1)
         p.add_argument("--optimizer", default="adagrad")
+        p.add_argument("--layout", default="position",
+                       choices=("position", "field"),
+                       help="widedeep / deepfm concat: by position in the "
+                            "row or by field (predict: the checkpoint's)")
+        p.add_argument("--pooling", default="sum", choices=("sum", "mean"),
+                       help="pooling of a field's entries under "
+                            "--layout field")
         p.add_argument("--device", default=None)
         p.add_argument("--seed", type=int, default=1234)
         p.add_argument("--save", default=None)

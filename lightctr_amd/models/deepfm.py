@@ -18,6 +18,17 @@ Entries past nf are left out of the concat only. forward_impl="fused" runs
 one pass over the batch each way (ops/csrc/deepfm_kernels.hip);
 "composed" runs the FM and embedding kernels side by side and is the
 baseline tools/bench_deepfm.py measures against.
+
+layout="field" addresses the concat by the entry's field instead of its
+position, with pooling="sum" or "mean" over the entries that share a field
+(models/embed_bag.py has the definition):
+
+    deep_in[r, c*K+k] = inv(r,c) sum_{j: fields[j] == c} E[f_j,k] x_j
+
+wide, s and fm still run over every entry of the row; an entry whose field
+is outside [0, nf) is left out of the concat only. "fused" then runs
+ops/csrc/embed_bag_kernels.hip's deepfm_bag_* pair, "composed" fm_forward +
+embed_bag_forward and fm_backward_emit + embed_bag_backward_emit + add.
 """
 
 from __future__ import annotations
@@ -29,6 +40,8 @@ import torch
 from ..ops import fm_ref
 from ..ops._extension import require_hip_ops, sort_ids
 from ..utils.metrics import auc_score
+from .embed_bag import (BagLayout, bag_dgather_cpu, bag_gather_cpu,
+                        load_checkpoint)
 from .mlp import MLP
 
 
@@ -55,6 +68,8 @@ class DeepFMHyper:
     dropout: float = 0.0
     init_sigma: float = 0.01
     seed: int = 1234
+    layout: str = "position"  # or "field": concat addressed by field
+    pooling: str = "sum"      # or "mean"; layout="field" only
 
 
 def _rows_pos(row_ptr):
@@ -66,7 +81,7 @@ def _rows_pos(row_ptr):
     return row_idx, pos
 
 
-class DeepFMModel:
+class DeepFMModel(BagLayout):
     def __init__(self, hyper: DeepFMHyper, device: str = "cpu",
                  max_batch_nnz: int = 1 << 22, forward_impl: str = "fused"):
         assert forward_impl in ("fused", "composed"), forward_impl
@@ -75,6 +90,7 @@ class DeepFMModel:
         self.device = torch.device(device)
         F, nf, K = hyper.num_features, hyper.num_fields, hyper.k
         assert K in (4, 8, 16, 32, 64)
+        self._init_bag(hyper, self.device)
         g = torch.Generator().manual_seed(hyper.seed)
         self.W = torch.zeros(F, device=self.device)  # wide LR weights
         self.E = (torch.randn(F, K, generator=g) * hyper.init_sigma).to(
@@ -100,9 +116,10 @@ class DeepFMModel:
             require_hip_ops()
 
     # -- CPU oracle pieces (plain fp32 torch) -------------------------------
-    def _fm_gather_cpu(self, row_ptr, fids, vals):
+    def _fm_gather_cpu(self, row_ptr, fids, vals, fields=None):
         """(fm [B], sumVX [B, K], deep_in [B, nf*K]) from one set of
-        products E[f] x."""
+        products E[f] x. fields: the concat is addressed by field and
+        pooled."""
         B = row_ptr.numel() - 1
         nf, K = self.h.num_fields, self.h.k
         row_idx, pos = _rows_pos(row_ptr)
@@ -112,34 +129,50 @@ class DeepFMModel:
         sq = torch.zeros(B, K).index_add_(0, row_idx, vx * vx)
         wide = torch.zeros(B).index_add_(0, row_idx, self.W[f] * vals)
         fm = wide + 0.5 * (sumVX * sumVX - sq).sum(dim=1)
+        if fields is not None:
+            return fm, sumVX, bag_gather_cpu(self.E, row_ptr, fields, fids,
+                                             vals, nf, self.h.pooling)
         deep_in = torch.zeros(B, nf * K)
         keep = pos < nf
         deep_in.view(B * nf, K)[(row_idx * nf + pos)[keep]] = vx[keep]
         return fm, sumVX, deep_in
 
-    def _emit_cpu(self, row_ptr, fids, vals, sumVX, dDeep, dpred):
+    def _emit_cpu(self, row_ptr, fids, vals, sumVX, dDeep, dpred,
+                  fields=None):
         """per-entry (gw [nnz], gv [nnz, K]) in the kernel's operation
-        order: gv = (D + d (s - E x)) x"""
+        order: gv = (D + d (s - E x)) x; under the field layout D is the
+        gradient of the entry's slot times the slot's inv"""
         B = row_ptr.numel() - 1
         nf, K = self.h.num_fields, self.h.k
         row_idx, pos = _rows_pos(row_ptr)
         x = vals.unsqueeze(1)
         d = dpred[row_idx].unsqueeze(1)
-        D = dDeep.reshape(B, nf, K)[row_idx, pos.clamp(max=nf - 1)]
-        D = torch.where((pos < nf).unsqueeze(1), D, torch.zeros_like(D))
+        if fields is not None:
+            D = bag_dgather_cpu(dDeep, row_ptr, fields, nf, K,
+                                self.h.pooling)
+        else:
+            D = dDeep.reshape(B, nf, K)[row_idx, pos.clamp(max=nf - 1)]
+            D = torch.where((pos < nf).unsqueeze(1), D, torch.zeros_like(D))
         gv = (D + d * (sumVX[row_idx] - self.E[fids.long()] * x)) * x
         return dpred[row_idx] * vals, gv
 
-    def _forward_cpu(self, row_ptr, fids, vals, train=True):
-        fm, sumVX, deep_in = self._fm_gather_cpu(row_ptr, fids, vals)
+    def _forward_cpu(self, row_ptr, fids, vals, train=True, fields=None):
+        fm, sumVX, deep_in = self._fm_gather_cpu(row_ptr, fids, vals, fields)
         deep = self.mlp.forward(deep_in, train=train)
         return fm + deep[:, 0], sumVX
 
     # -- GPU ----------------------------------------------------------------
-    def _forward_gpu(self, row_ptr, fids, vals, train=True):
+    def _forward_gpu(self, row_ptr, fids, vals, train=True, fields=None):
         ops = require_hip_ops()
         nf = self.h.num_fields
-        if self.forward_impl == "fused":
+        if fields is not None and self.forward_impl == "fused":
+            fm, sumVX, deep_in = ops.deepfm_bag_forward(
+                row_ptr, fields, fids, vals, self.W, self.E, nf, self._pool)
+        elif fields is not None:
+            fm, sumVX = ops.fm_forward(row_ptr, fids, vals, self.W, self.E)
+            deep_in = ops.embed_bag_forward(row_ptr, fields, fids, vals,
+                                            self.E, nf, self._pool)
+        elif self.forward_impl == "fused":
             fm, sumVX, deep_in = ops.deepfm_forward(row_ptr, fids, vals,
                                                     self.W, self.E, nf)
         else:
@@ -150,35 +183,48 @@ class DeepFMModel:
         deep = self.mlp.forward(deep_in, train=train)
         return fm + deep[:, 0], sumVX
 
-    def _emit_gpu(self, ops, row_ptr, fids, vals, sumVX, dDeep, dpred):
+    def _emit_gpu(self, ops, row_ptr, fids, vals, sumVX, dDeep, dpred,
+                  fields=None):
         nf = self.h.num_fields
+        if fields is not None and self.forward_impl == "fused":
+            return ops.deepfm_bag_backward_emit(row_ptr, fields, fids, vals,
+                                                self.E, sumVX, dDeep, dpred,
+                                                nf, self._pool)
         if self.forward_impl == "fused":
             return ops.deepfm_backward_emit(row_ptr, fids, vals, self.E,
                                             sumVX, dDeep, dpred, nf)
         gw, gv_fm = ops.fm_backward_emit(row_ptr, fids, vals, self.E, sumVX,
                                          dpred, None)
         # the binding wants a dwide tensor; its gw repeats the FM emit's
-        _, gv_deep = ops.embed_backward_emit(row_ptr, vals, dDeep, dpred, nf,
-                                             self.h.k)
+        if fields is not None:
+            _, gv_deep = ops.embed_bag_backward_emit(
+                row_ptr, fields, vals, dDeep, dpred, nf, self.h.k,
+                self._pool)
+        else:
+            _, gv_deep = ops.embed_backward_emit(row_ptr, vals, dDeep, dpred,
+                                                 nf, self.h.k)
         return gw, gv_fm + gv_deep
 
-    def predict_proba(self, row_ptr, fids, vals):
+    def predict_proba(self, row_ptr, fids, vals, fields=None):
         fwd = self._forward_gpu if self._gpu else self._forward_cpu
-        score, _ = fwd(row_ptr, fids, vals, train=False)
+        score, _ = fwd(row_ptr, fids, vals, train=False,
+                       fields=self._fields(fields))
         return torch.sigmoid(torch.clamp(score, -16, 16))
 
-    def train_step(self, row_ptr, fids, vals, labels):
+    def train_step(self, row_ptr, fids, vals, labels, fields=None):
         B = row_ptr.numel() - 1
+        fields = self._fields(fields)
         if B == 0:
             return torch.zeros(0, device=self.device)
         scale = 1.0 / B
         if self._gpu:
             ops = require_hip_ops()
-            score, sumVX = self._forward_gpu(row_ptr, fids, vals)
+            score, sumVX = self._forward_gpu(row_ptr, fids, vals,
+                                             fields=fields)
             loss, dpred = ops.logloss_grad(score, labels, scale)
             dDeep = self.mlp.backward(dpred.unsqueeze(1))  # [B, nf*K]
             gw, gv = self._emit_gpu(ops, row_ptr, fids, vals, sumVX,
-                                    dDeep.contiguous(), dpred)
+                                    dDeep.contiguous(), dpred, fields)
             sorted_fids, perm = sort_ids(fids, self.h.num_features)
             ops.fm_sorted_apply(sorted_fids, perm, gw, gv, self.gradW,
                                 self.gradE, self.touched)
@@ -200,10 +246,11 @@ class DeepFMModel:
             self.mlp.apply_grads()
             return loss
         # CPU oracle
-        score, sumVX = self._forward_cpu(row_ptr, fids, vals)
+        score, sumVX = self._forward_cpu(row_ptr, fids, vals, fields=fields)
         loss, dpred = fm_ref.logloss_grad_ref(score, labels, scale)
         dDeep = self.mlp.backward(dpred.unsqueeze(1))
-        gw, gv = self._emit_cpu(row_ptr, fids, vals, sumVX, dDeep, dpred)
+        gw, gv = self._emit_cpu(row_ptr, fids, vals, sumVX, dDeep, dpred,
+                                fields)
         f = fids.long()
         self.gradW.index_add_(0, f, gw)
         self.gradE.index_add_(0, f, gv)
@@ -235,7 +282,7 @@ class DeepFMModel:
         torch.save(self.state_dict(), path)
 
     def load(self, path):
-        d = torch.load(path, map_location=self.device, weights_only=True)
+        d = load_checkpoint(path, self.device)
         self.W.copy_(d["W"]); self.E.copy_(d["E"])
         self.nW.copy_(d["nW"]); self.nE.copy_(d["nE"])
         if self.h.optimizer == "ftrl" and "zW" in d:
@@ -260,7 +307,7 @@ class DeepFMTrainer:
             for s in range(0, N, self.batch_size):
                 b = ds.slice_rows(s, min(s + self.batch_size, N))
                 loss = self.model.train_step(b.row_ptr, b.fids, b.vals,
-                                             b.labels)
+                                             b.labels, fields=b.fields)
                 tot += float(loss.mean()); nb += 1
             if log:
                 log(f"epoch {ep}: loss={tot / max(nb, 1):.5f}")
@@ -268,7 +315,8 @@ class DeepFMTrainer:
 
     def evaluate(self, dataset=None):
         ds = (dataset or self.ds).to(self.device)
-        p = self.model.predict_proba(ds.row_ptr, ds.fids, ds.vals)
+        p = self.model.predict_proba(ds.row_ptr, ds.fids, ds.vals,
+                                     fields=ds.fields)
         loss = torch.nn.functional.binary_cross_entropy(
             p.clamp(1e-7, 1 - 1e-7), ds.labels)
         return {"auc": auc_score(p.cpu(), ds.labels.cpu()),

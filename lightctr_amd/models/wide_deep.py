@@ -5,7 +5,17 @@ trainer (/root/reference/LightCTR/distributed_algo_abst.h:105-280: wide LR
 over hashed features + per-field embeddings concatenated into a 2-layer MLP)
 — rebuilt single-device-first: fused embedding gather (bf16) -> 3-layer MFMA
 MLP -> sorted segment-reduce embedding backward + fused sparse optimizer.
-Fixed-fields rows (e.g. Criteo 39) required for the concat layout.
+
+Two concat layouts. layout="position" (default) puts an entry at its position
+in the row and suits fixed-fields rows (e.g. Criteo 39, one value per field,
+always in the same order). layout="field" puts it at its field,
+
+    deep_in[r, c*K+k] = pool_{j in row r, fields[j] == c} E[f_j,k] x_j
+
+with pooling="sum" or "mean" (by the number of entries in the slot), empty
+slots +0 and entries of a field outside [0, num_fields) left out of the deep
+part only: rows with missing fields, multi-valued fields and any token order
+are laid out right (ops/csrc/embed_bag_kernels.hip).
 """
 
 from __future__ import annotations
@@ -17,6 +27,8 @@ import torch
 from ..ops import fm_ref
 from ..ops._extension import require_hip_ops, sort_ids
 from ..utils.metrics import auc_score
+from .embed_bag import (BagLayout, bag_dgather_cpu, bag_gather_cpu,
+                        load_checkpoint)
 from .mlp import MLP
 
 
@@ -40,15 +52,18 @@ class WideDeepHyper:
     dropout: float = 0.0
     init_sigma: float = 0.01
     seed: int = 1234
+    layout: str = "position"  # or "field": concat addressed by field
+    pooling: str = "sum"      # or "mean"; layout="field" only
 
 
-class WideDeepModel:
+class WideDeepModel(BagLayout):
     def __init__(self, hyper: WideDeepHyper, device: str = "cpu",
                  max_batch_nnz: int = 1 << 22):
         self.h = hyper
         self.device = torch.device(device)
         F, nf, K = hyper.num_features, hyper.num_fields, hyper.k
         assert K in (4, 8, 16, 32, 64)
+        self._init_bag(hyper, self.device)
         g = torch.Generator().manual_seed(hyper.seed)
         self.W = torch.zeros(F, device=self.device)  # wide LR weights
         self.E = (torch.randn(F, K, generator=g) * hyper.init_sigma).to(
@@ -87,40 +102,57 @@ class WideDeepModel:
         out.view(B * nf, K).index_add_(0, flat_idx[keep], emb[keep])
         return out
 
-    def _forward_gpu(self, row_ptr, fids, vals, train=True):
+    def _forward_gpu(self, row_ptr, fids, vals, train=True, fields=None):
         ops = require_hip_ops()
         wide = ops.wide_forward(row_ptr, fids, vals, self.W)
-        deep_in = ops.embed_gather(row_ptr, fids, vals, self.E,
-                                   self.h.num_fields)
+        if fields is not None:
+            deep_in = ops.embed_bag_forward(row_ptr, fields, fids, vals,
+                                            self.E, self.h.num_fields,
+                                            self._pool)
+        else:
+            deep_in = ops.embed_gather(row_ptr, fids, vals, self.E,
+                                       self.h.num_fields)
         deep = self.mlp.forward(deep_in, train=train)
         return wide + deep[:, 0], wide
 
-    def _forward_cpu(self, row_ptr, fids, vals, train=True):
+    def _forward_cpu(self, row_ptr, fids, vals, train=True, fields=None):
         B = row_ptr.numel() - 1
         rp = row_ptr.long()
         row_idx = torch.repeat_interleave(torch.arange(B), rp[1:] - rp[:-1])
         wide = torch.zeros(B)
         wide.index_add_(0, row_idx, self.W[fids.long()] * vals)
-        deep_in = self._gather_cpu(row_ptr, fids, vals)
+        if fields is not None:
+            deep_in = bag_gather_cpu(self.E, row_ptr, fields, fids, vals,
+                                     self.h.num_fields, self.h.pooling)
+        else:
+            deep_in = self._gather_cpu(row_ptr, fids, vals)
         deep = self.mlp.forward(deep_in, train=train)
         return wide + deep[:, 0], wide
 
-    def predict_proba(self, row_ptr, fids, vals):
+    def predict_proba(self, row_ptr, fids, vals, fields=None):
         fwd = self._forward_gpu if self._gpu else self._forward_cpu
-        pred, _ = fwd(row_ptr, fids, vals, train=False)
+        pred, _ = fwd(row_ptr, fids, vals, train=False,
+                      fields=self._fields(fields))
         return torch.sigmoid(torch.clamp(pred, -16, 16))
 
-    def train_step(self, row_ptr, fids, vals, labels):
+    def train_step(self, row_ptr, fids, vals, labels, fields=None):
         B = row_ptr.numel() - 1
         scale = 1.0 / B
+        fields = self._fields(fields)
         if self._gpu:
             ops = require_hip_ops()
-            pred, wide = self._forward_gpu(row_ptr, fids, vals)
+            pred, wide = self._forward_gpu(row_ptr, fids, vals,
+                                           fields=fields)
             loss, dpred = ops.logloss_grad(pred, labels, scale)
             dDeep = self.mlp.backward(dpred.unsqueeze(1))  # [B, nf*K]
-            gw, gv = ops.embed_backward_emit(row_ptr, vals,
-                                             dDeep.contiguous(), dpred,
-                                             self.h.num_fields, self.h.k)
+            if fields is not None:
+                gw, gv = ops.embed_bag_backward_emit(
+                    row_ptr, fields, vals, dDeep.contiguous(), dpred,
+                    self.h.num_fields, self.h.k, self._pool)
+            else:
+                gw, gv = ops.embed_backward_emit(row_ptr, vals,
+                                                 dDeep.contiguous(), dpred,
+                                                 self.h.num_fields, self.h.k)
             sorted_fids, perm = sort_ids(fids, self.h.num_features)
             ops.fm_sorted_apply(sorted_fids, perm, gw, gv, self.gradW,
                                 self.gradE, self.touched)
@@ -142,7 +174,7 @@ class WideDeepModel:
             self.mlp.apply_grads()
             return loss
         # CPU oracle
-        pred, wide = self._forward_cpu(row_ptr, fids, vals)
+        pred, wide = self._forward_cpu(row_ptr, fids, vals, fields=fields)
         loss, dpred = fm_ref.logloss_grad_ref(pred, labels, scale)
         dDeep = self.mlp.backward(dpred.unsqueeze(1))
         rp = row_ptr.long()
@@ -153,9 +185,14 @@ class WideDeepModel:
         x = vals
         self.gradW.index_add_(0, f, dpred[row_idx] * x)
         nf, K = self.h.num_fields, self.h.k
-        dE = dDeep.view(B, nf, K)[row_idx, pos.clamp(max=nf - 1)] \
-            * x.unsqueeze(1)
-        dE = torch.where((pos < nf).unsqueeze(1), dE, torch.zeros_like(dE))
+        if fields is not None:
+            dE = bag_dgather_cpu(dDeep, row_ptr, fields, nf, K,
+                                 self.h.pooling) * x.unsqueeze(1)
+        else:
+            dE = dDeep.view(B, nf, K)[row_idx, pos.clamp(max=nf - 1)] \
+                * x.unsqueeze(1)
+            dE = torch.where((pos < nf).unsqueeze(1), dE,
+                             torch.zeros_like(dE))
         self.gradE.index_add_(0, f, dE)
         uniq = torch.unique(f).int()
         if self.h.optimizer == "ftrl":
@@ -181,7 +218,7 @@ class WideDeepModel:
         torch.save(self.state_dict(), path)
 
     def load(self, path):
-        d = torch.load(path, map_location=self.device, weights_only=True)
+        d = load_checkpoint(path, self.device)
         self.W.copy_(d["W"]); self.E.copy_(d["E"])
         self.nW.copy_(d["nW"]); self.nE.copy_(d["nE"])
         self.mlp.load_state_dict(d["mlp"])
@@ -203,7 +240,7 @@ class WideDeepTrainer:
             for s in range(0, N, self.batch_size):
                 b = ds.slice_rows(s, min(s + self.batch_size, N))
                 loss = self.model.train_step(b.row_ptr, b.fids, b.vals,
-                                             b.labels)
+                                             b.labels, fields=b.fields)
                 tot += float(loss.mean()); nb += 1
             if log:
                 log(f"epoch {ep}: loss={tot / max(nb, 1):.5f}")
@@ -211,7 +248,8 @@ class WideDeepTrainer:
 
     def evaluate(self, dataset=None):
         ds = (dataset or self.ds).to(self.device)
-        p = self.model.predict_proba(ds.row_ptr, ds.fids, ds.vals)
+        p = self.model.predict_proba(ds.row_ptr, ds.fids, ds.vals,
+                                     fields=ds.fields)
         loss = torch.nn.functional.binary_cross_entropy(
             p.clamp(1e-7, 1 - 1e-7), ds.labels)
         return {"auc": auc_score(p.cpu(), ds.labels.cpu()),

@@ -1797,6 +1797,125 @@ std::vector<at::Tensor> deepfm_backward_emit(
   return {gw, gv};
 }
 
+// ---- field-addressed embedding bags ----
+
+// The forward kernels stage one [nf, K] fp32 slice and nf counters per wave
+// in dynamic LDS; a request past the per-block limit is a launch error that
+// would leave the outputs unwritten. Checked by all four bindings, so a
+// forward that is accepted has a backward that is.
+void check_bag_args(const at::Tensor& fields, const at::Tensor& fids,
+                    int64_t nf, int K, int64_t pooling, const char* op) {
+  check_i32_n(fields, fids.numel(), "fields");
+  CHK(pooling == 0 || pooling == 1, op,
+      ": pooling must be 0 (sum) or 1 (mean), got ", pooling);
+  CHK(nf >= 1, "nf must be >= 1");
+  CHK(nf * K <= std::numeric_limits<int>::max() / 32,
+      "nf * K must fit an int");
+  const long need = lightctr::embed_bag_lds_bytes((int)nf, K);
+  const long have = lightctr::ffm_max_lds_per_block();
+  CHK(need <= have, op, ": nf=", nf, ", K=", K, " needs ", need,
+      " bytes of LDS per block, the device gives ", have);
+}
+
+// bf16 concat [B, nf*K] addressed by field, sum (0) or mean (1) pooled
+at::Tensor embed_bag_forward(at::Tensor row_ptr, at::Tensor fields,
+                             at::Tensor fids, at::Tensor vals, at::Tensor E,
+                             int64_t nf, int64_t pooling) {
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_deepfm_e(E);
+  check_bag_args(fields, fids, nf, K, pooling, "embed_bag_forward");
+  auto out = at::empty({B, nf * K}, E.options().dtype(at::kBFloat16));
+  if (B == 0) return out;  // nothing is launched
+  lightctr::embed_bag_forward_launch(
+      row_ptr.data_ptr<int>(), fields.data_ptr<int>(), fids.data_ptr<int>(),
+      vals.data_ptr<float>(), E.data_ptr<float>(), out.data_ptr(), (int)nf,
+      (int)pooling, B, K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return out;
+}
+
+// gv = dOut[r, c*K+k] inv x, gw = dwide[r] x
+std::vector<at::Tensor> embed_bag_backward_emit(
+    at::Tensor row_ptr, at::Tensor fields, at::Tensor vals, at::Tensor dOut,
+    at::Tensor dwide, int64_t nf, int64_t K, int64_t pooling) {
+  check_cuda_i32(row_ptr, "row_ptr");
+  check_cuda_f32(vals, "vals");
+  CHK(row_ptr.numel() >= 1, "row_ptr must hold B + 1 offsets");
+  const int B = (int)row_ptr.numel() - 1;
+  check_embed_k(K);
+  check_bag_args(fields, vals, nf, (int)K, pooling,
+                 "embed_bag_backward_emit");
+  check_cuda_f32(dOut, "dOut");
+  CHK(dOut.dim() == 2 && dOut.size(0) == B && dOut.size(1) == nf * K,
+      "dOut must be [B, nf*K]");
+  check_cuda_f32(dwide, "dwide");
+  CHK(dwide.dim() == 1 && dwide.size(0) == B, "dwide must be [B]");
+  const auto nnz = vals.numel();
+  auto gw = at::empty({nnz}, dOut.options());
+  auto gv = at::empty({nnz, K}, dOut.options());
+  if (B == 0 || nnz == 0) return {gw, gv};
+  lightctr::embed_bag_backward_emit_launch(
+      row_ptr.data_ptr<int>(), fields.data_ptr<int>(),
+      vals.data_ptr<float>(), dOut.data_ptr<float>(),
+      dwide.data_ptr<float>(), gw.data_ptr<float>(), gv.data_ptr<float>(),
+      (int)nf, (int)pooling, B, (int)K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {gw, gv};
+}
+
+// deepfm_forward with the concat addressed by field
+std::vector<at::Tensor> deepfm_bag_forward(at::Tensor row_ptr,
+                                           at::Tensor fields, at::Tensor fids,
+                                           at::Tensor vals, at::Tensor W,
+                                           at::Tensor E, int64_t nf,
+                                           int64_t pooling) {
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_deepfm_e(E);
+  check_f32_n(W, E.size(0), "W");
+  check_bag_args(fields, fids, nf, K, pooling, "deepfm_bag_forward");
+  auto fm = at::empty({B}, E.options());
+  auto sumVX = at::empty({B, K}, E.options());
+  auto deep_in = at::empty({B, nf * K}, E.options().dtype(at::kBFloat16));
+  if (B == 0) return {fm, sumVX, deep_in};  // nothing is launched
+  lightctr::deepfm_bag_forward_launch(
+      row_ptr.data_ptr<int>(), fields.data_ptr<int>(), fids.data_ptr<int>(),
+      vals.data_ptr<float>(), W.data_ptr<float>(), E.data_ptr<float>(),
+      deep_in.data_ptr(), sumVX.data_ptr<float>(), fm.data_ptr<float>(),
+      (int)nf, (int)pooling, B, K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {fm, sumVX, deep_in};
+}
+
+// deepfm_backward_emit with D read at the entry's field and scaled by inv
+std::vector<at::Tensor> deepfm_bag_backward_emit(
+    at::Tensor row_ptr, at::Tensor fields, at::Tensor fids, at::Tensor vals,
+    at::Tensor E, at::Tensor sumVX, at::Tensor dDeep, at::Tensor dpred,
+    int64_t nf, int64_t pooling) {
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_deepfm_e(E);
+  check_bag_args(fields, fids, nf, K, pooling, "deepfm_bag_backward_emit");
+  check_cuda_f32(sumVX, "sumVX");
+  CHK(sumVX.dim() == 2 && sumVX.size(0) == B && sumVX.size(1) == K,
+      "sumVX must be [B, K]");
+  check_cuda_f32(dDeep, "dDeep");
+  CHK(dDeep.dim() == 2 && dDeep.size(0) == B && dDeep.size(1) == nf * K,
+      "dDeep must be [B, nf*K]");
+  check_cuda_f32(dpred, "dpred");
+  CHK(dpred.dim() == 1 && dpred.size(0) == B, "dpred must be [B]");
+  const auto nnz = fids.numel();
+  auto gw = at::empty({nnz}, E.options());
+  auto gv = at::empty({nnz, K}, E.options());
+  if (B == 0 || nnz == 0) return {gw, gv};
+  lightctr::deepfm_bag_backward_emit_launch(
+      row_ptr.data_ptr<int>(), fields.data_ptr<int>(), fids.data_ptr<int>(),
+      vals.data_ptr<float>(), E.data_ptr<float>(), sumVX.data_ptr<float>(),
+      dDeep.data_ptr<float>(), dpred.data_ptr<float>(),
+      gw.data_ptr<float>(), gv.data_ptr<float>(), (int)nf, (int)pooling, B,
+      K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {gw, gv};
+}
+
 // ---- native data loader ----
 // Fast single-pass libffm parser ("label field:fid:val" per line) —
 // native equivalent of the reference's C++ loader
@@ -2373,6 +2492,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embed_gather", &embed_gather, "concat embedding gather -> bf16");
   m.def("embed_backward_emit", &embed_backward_emit,
         "per-entry embedding grads (gw, gv) for sorted apply");
+  m.def("embed_bag_forward", &embed_bag_forward,
+        "field-addressed pooled embedding bag -> bf16 concat [B, nf*K]");
+  m.def("embed_bag_backward_emit", &embed_bag_backward_emit,
+        "per-entry grads (gw, gv) of the field-addressed bag");
+  m.def("deepfm_bag_forward", &deepfm_bag_forward,
+        "DeepFM fused forward, concat addressed by field: (fm, sumVX, "
+        "deep_in bf16)");
+  m.def("deepfm_bag_backward_emit", &deepfm_bag_backward_emit,
+        "DeepFM fused per-entry gradients, concat addressed by field: "
+        "(gw, gv)");
+  m.def("embed_bag_lds_bytes", &lightctr::embed_bag_lds_bytes,
+        "dynamic LDS per block of the embed_bag / deepfm_bag forward",
+        py::arg("nf"), py::arg("K"));
   m.def("wide_forward", &wide_forward, "LR wide forward sum");
   m.def("w2v_negsample_step", &w2v_negsample_step,
         "fused CBOW negative-sampling train step (Hogwild)");

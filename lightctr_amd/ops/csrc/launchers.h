@@ -313,6 +313,31 @@ void deepfm_backward_emit_launch(const int* row_ptr, const int* fids,
                                  const float* dpred, float* gw, float* gv,
                                  int nf, int B, int K, ihipStream_t* stream);
 
+// --- embed_bag_kernels.hip ---
+long embed_bag_lds_bytes(int nf, int K);
+void embed_bag_forward_launch(const int* row_ptr, const int* fields,
+                              const int* fids, const float* vals,
+                              const float* E, void* out_bf, int nf,
+                              int pooling, int B, int K,
+                              ihipStream_t* stream);
+void embed_bag_backward_emit_launch(const int* row_ptr, const int* fields,
+                                    const float* vals, const float* dOut,
+                                    const float* dwide, float* gw, float* gv,
+                                    int nf, int pooling, int B, int K,
+                                    ihipStream_t* stream);
+void deepfm_bag_forward_launch(const int* row_ptr, const int* fields,
+                               const int* fids, const float* vals,
+                               const float* W, const float* E, void* out_bf,
+                               float* sumVX, float* fm, int nf, int pooling,
+                               int B, int K, ihipStream_t* stream);
+void deepfm_bag_backward_emit_launch(const int* row_ptr, const int* fields,
+                                     const int* fids, const float* vals,
+                                     const float* E, const float* sumVX,
+                                     const float* dDeep, const float* dpred,
+                                     float* gw, float* gv, int nf,
+                                     int pooling, int B, int K,
+                                     ihipStream_t* stream);
+
 // --- codec_kernels.hip ---
 void quantile_encode_launch(const float* x, unsigned char* code,
                             const float* table, int levels, long n,

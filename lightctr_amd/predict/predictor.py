@@ -22,8 +22,15 @@ class BatchPredictor:
         """ds: LibffmDataset on the model's device."""
         out = []
         N = ds.num_rows
+        # Wide&Deep / DeepFM with the concat addressed by field
+        by_field = getattr(getattr(self.model, "h", None), "layout",
+                           "position") == "field"
         for s in range(0, N, self.batch_size):
             b = ds.slice_rows(s, min(s + self.batch_size, N))
+            if by_field:
+                out.append(self.model.predict_proba(b.row_ptr, b.fids,
+                                                    b.vals, fields=b.fields))
+                continue
             try:
                 p = self.model.predict_proba(b.row_ptr, b.fids, b.vals)
             except TypeError:  # field-aware models take fields too
