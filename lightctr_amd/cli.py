@@ -7,6 +7,8 @@ command:
 
     python -m lightctr_amd.cli train --model fm --data path.csv --epochs 5
     python -m lightctr_amd.cli train --model ffm|nfm|widedeep|deepfm|gbm ...
+    python -m lightctr_amd.cli train|predict --model fwfm --data path.csv ...
+        (field-weighted FM; num_fields comes from the data)
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
     python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
         --data dense.csv ...      (dense rows; served by the compiled forest)
@@ -48,7 +50,8 @@ def _load_data(args):
 
 def cmd_train(args) -> int:
     dev = _device(args)
-    if args.model not in ("fm", "ffm", "nfm", "widedeep", "deepfm", "lr"):
+    if args.model not in ("fm", "ffm", "fwfm", "nfm", "widedeep", "deepfm",
+                          "lr"):
         # the rest of the zoo reads dense / text data, not libffm
         return _train_other(args, dev)
     ds = _load_data(args)
@@ -68,6 +71,14 @@ def cmd_train(args) -> int:
                                      optimizer=args.optimizer, lr=args.lr),
                         device=dev, batch_size=args.batch,
                         epochs=args.epochs)
+    elif args.model == "fwfm":
+        from .models.fwfm import FwFMHyper, FwFMTrainer
+
+        tr = FwFMTrainer(ds, FwFMHyper(num_features=F,
+                                       num_fields=ds.num_fields, k=args.k,
+                                       optimizer=args.optimizer, lr=args.lr),
+                         device=dev, batch_size=args.batch,
+                         epochs=args.epochs)
     elif args.model == "nfm":
         from .models.nfm import NFMHyper, NFMTrainer
 
@@ -425,6 +436,17 @@ def cmd_predict(args) -> int:
         model = FFMModel(FFMHyper(num_features=F,
                                   num_fields=ds.num_fields, k=args.k),
                          device=dev)
+    elif args.model == "fwfm":
+        from .models.fwfm import FwFMHyper, FwFMModel
+
+        # R is [nf, nf]: a checkpoint names the field count it was trained
+        # with (a data file need not carry the last field in any row)
+        nf = ds.num_fields
+        if args.load:
+            ckpt = torch.load(args.load, map_location=dev, weights_only=True)
+            nf = ckpt.get("hyper", {}).get("num_fields", nf)
+        model = FwFMModel(FwFMHyper(num_features=F, num_fields=nf, k=args.k,
+                                    optimizer=args.optimizer), device=dev)
     elif args.model == "nfm":
         from .models.nfm import NFMHyper, NFMModel
 

@@ -1,5 +1,6 @@
 from .fm import FMModel, FMTrainer, FMHyper
 from .ffm import FFMModel, FFMTrainer, FFMHyper
+from .fwfm import FwFMModel, FwFMTrainer, FwFMHyper
 from .nfm import NFMModel, NFMTrainer, NFMHyper
 from .wide_deep import WideDeepModel, WideDeepTrainer, WideDeepHyper
 from .deepfm import DeepFMModel, DeepFMTrainer, DeepFMHyper
@@ -17,6 +18,7 @@ from .gbdt_lr import GBDTLRModel, GBDTLRHyper
 __all__ = [
     "FMModel", "FMTrainer", "FMHyper",
     "FFMModel", "FFMTrainer", "FFMHyper",
+    "FwFMModel", "FwFMTrainer", "FwFMHyper",
     "NFMModel", "NFMTrainer", "NFMHyper",
     "WideDeepModel", "WideDeepTrainer", "WideDeepHyper",
     "DeepFMModel", "DeepFMTrainer", "DeepFMHyper",

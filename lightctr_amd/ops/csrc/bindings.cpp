@@ -1916,6 +1916,71 @@ std::vector<at::Tensor> deepfm_bag_backward_emit(
   return {gw, gv};
 }
 
+// ---- field-weighted FM ----
+
+// Shared argument checks of the two FwFM bindings; returns nf. Both kernels
+// keep Rs and per-wave [nf, K] tiles in dynamic LDS; the backward needs the
+// most, and its figure is the one rule, so a forward that is accepted has a
+// backward that is.
+int check_fwfm_args(const at::Tensor& fields, const at::Tensor& fids,
+                    const at::Tensor& R, int K, const char* op) {
+  check_i32_n(fields, fids.numel(), "fields");
+  check_cuda_f32(R, "R");
+  CHK(R.dim() == 2 && R.size(0) == R.size(1) && R.size(0) >= 1, op,
+      ": R must be [nf, nf]");
+  CHK(R.size(0) <= 1024, op, ": nf must be <= 1024, got ", R.size(0));
+  const int nf = (int)R.size(0);
+  const long need = lightctr::fwfm_lds_bytes(nf, K);
+  const long have = lightctr::ffm_max_lds_per_block();
+  CHK(need <= have, op, ": nf=", nf, ", K=", K, " needs ", need,
+      " bytes of LDS per block, the device gives ", have);
+  return nf;
+}
+
+// pred[B] = wide + field-weighted pair term; nothing of size [B, nf, K]
+at::Tensor fwfm_forward(at::Tensor row_ptr, at::Tensor fields,
+                        at::Tensor fids, at::Tensor vals, at::Tensor W,
+                        at::Tensor V, at::Tensor R) {
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_fm_v(V);
+  check_f32_n(W, V.size(0), "W");
+  const int nf = check_fwfm_args(fields, fids, R, K, "fwfm_forward");
+  auto pred = at::empty({B}, V.options());
+  if (B == 0) return pred;  // nothing is launched
+  lightctr::fwfm_forward_launch(
+      row_ptr.data_ptr<int>(), fields.data_ptr<int>(), fids.data_ptr<int>(),
+      vals.data_ptr<float>(), W.data_ptr<float>(), V.data_ptr<float>(),
+      R.data_ptr<float>(), pred.data_ptr<float>(), nf, B, K, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return pred;
+}
+
+// (gw [nnz], gv [nnz, K], dR [nf, nf]); S and T are recomputed per row
+std::vector<at::Tensor> fwfm_backward_emit(at::Tensor row_ptr,
+                                           at::Tensor fields, at::Tensor fids,
+                                           at::Tensor vals, at::Tensor V,
+                                           at::Tensor R, at::Tensor dpred) {
+  const int B = check_fm_csr(row_ptr, fids, vals);
+  const int K = check_fm_v(V);
+  const int nf = check_fwfm_args(fields, fids, R, K, "fwfm_backward_emit");
+  check_f32_n(dpred, B, "dpred");
+  const auto nnz = fids.numel();
+  auto gw = at::empty({nnz}, V.options());
+  auto gv = at::empty({nnz, K}, V.options());
+  auto dR = at::empty({nf, nf}, V.options());
+  auto partial = at::empty(
+      {lightctr::fwfm_backward_blocks(B), (int64_t)nf * (nf + 1) / 2},
+      V.options());
+  lightctr::fwfm_backward_emit_launch(
+      row_ptr.data_ptr<int>(), fields.data_ptr<int>(), fids.data_ptr<int>(),
+      vals.data_ptr<float>(), V.data_ptr<float>(), R.data_ptr<float>(),
+      dpred.data_ptr<float>(), gw.data_ptr<float>(), gv.data_ptr<float>(),
+      partial.data_ptr<float>(), dR.data_ptr<float>(), nf, B, K,
+      cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {gw, gv, dR};
+}
+
 // ---- native data loader ----
 // Fast single-pass libffm parser ("label field:fid:val" per line) —
 // native equivalent of the reference's C++ loader
@@ -2505,6 +2570,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embed_bag_lds_bytes", &lightctr::embed_bag_lds_bytes,
         "dynamic LDS per block of the embed_bag / deepfm_bag forward",
         py::arg("nf"), py::arg("K"));
+  m.def("fwfm_forward", &fwfm_forward,
+        "field-weighted FM forward: pred [B]");
+  m.def("fwfm_backward_emit", &fwfm_backward_emit,
+        "field-weighted FM per-entry gradients and dR: (gw, gv, dR)");
+  m.def("fwfm_lds_bytes", &lightctr::fwfm_lds_bytes,
+        "dynamic LDS per block the FwFM kernels need", py::arg("nf"),
+        py::arg("K"));
   m.def("wide_forward", &wide_forward, "LR wide forward sum");
   m.def("w2v_negsample_step", &w2v_negsample_step,
         "fused CBOW negative-sampling train step (Hogwild)");

@@ -338,6 +338,20 @@ void deepfm_bag_backward_emit_launch(const int* row_ptr, const int* fields,
                                      int pooling, int B, int K,
                                      ihipStream_t* stream);
 
+// --- fwfm_kernels.hip ---
+long fwfm_lds_bytes(int nf, int K);
+int fwfm_backward_blocks(int B);
+void fwfm_forward_launch(const int* row_ptr, const int* fields,
+                         const int* fids, const float* vals, const float* W,
+                         const float* V, const float* R, float* pred, int nf,
+                         int B, int K, ihipStream_t* stream);
+void fwfm_backward_emit_launch(const int* row_ptr, const int* fields,
+                               const int* fids, const float* vals,
+                               const float* V, const float* R,
+                               const float* dpred, float* gw, float* gv,
+                               float* partial, float* dR, int nf, int B,
+                               int K, ihipStream_t* stream);
+
 // --- codec_kernels.hip ---
 void quantile_encode_launch(const float* x, unsigned char* code,
                             const float* table, int levels, long n,
