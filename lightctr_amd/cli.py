@@ -9,6 +9,8 @@ command:
     python -m lightctr_amd.cli train --model ffm|nfm|widedeep|deepfm|gbm ...
     python -m lightctr_amd.cli train|predict --model fwfm --data path.csv ...
         (field-weighted FM; num_fields comes from the data)
+    python -m lightctr_amd.cli train|predict --model dcn --cross-layers 3 ...
+        (Deep & Cross; --layout / --pooling as for widedeep)
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
     python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
         --data dense.csv ...      (dense rows; served by the compiled forest)
@@ -51,7 +53,7 @@ def _load_data(args):
 def cmd_train(args) -> int:
     dev = _device(args)
     if args.model not in ("fm", "ffm", "fwfm", "nfm", "widedeep", "deepfm",
-                          "lr"):
+                          "dcn", "lr"):
         # the rest of the zoo reads dense / text data, not libffm
         return _train_other(args, dev)
     ds = _load_data(args)
@@ -110,6 +112,17 @@ def cmd_train(args) -> int:
                                            pooling=args.pooling),
                            device=dev, batch_size=args.batch,
                            epochs=args.epochs)
+    elif args.model == "dcn":
+        from .models.dcn import DCNHyper, DCNTrainer
+
+        tr = DCNTrainer(ds, DCNHyper(num_features=F,
+                                     num_fields=ds.num_fields, k=args.k,
+                                     optimizer=args.optimizer, lr=args.lr,
+                                     layout=args.layout,
+                                     pooling=args.pooling,
+                                     cross_layers=args.cross_layers),
+                        device=dev, batch_size=args.batch,
+                        epochs=args.epochs)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRTrainer
 
@@ -404,8 +417,8 @@ def _predict_dense(args, dev) -> int:
 
 
 def _concat_setup(args, ds, dev):
-    """(checkpoint dict or None, hyper keywords) of a Wide&Deep / DeepFM
-    model to predict with. The checkpoint is read once; num_fields, layout
+    """(checkpoint dict or None, hyper keywords) of a Wide&Deep / DeepFM /
+    DCN model to predict with. The checkpoint is read once; num_fields, layout
     and pooling are its hyper's where it names them (a data file need not
     carry the last field in any row), else the data's and the flags'."""
     kw = {"num_fields": ds.num_fields, "layout": args.layout,
@@ -466,6 +479,16 @@ def cmd_predict(args) -> int:
         model = DeepFMModel(DeepFMHyper(num_features=F, k=args.k,
                                         optimizer=args.optimizer, **kw),
                             device=dev)
+    elif args.model == "dcn":
+        from .models.dcn import DCNHyper, DCNModel
+
+        # Wc is [cross_layers, nf*k]: the checkpoint's depth where it has one
+        ckpt, kw = _concat_setup(args, ds, dev)
+        L = (ckpt or {}).get("hyper", {}).get("cross_layers",
+                                              args.cross_layers)
+        model = DCNModel(DCNHyper(num_features=F, k=args.k,
+                                  optimizer=args.optimizer, cross_layers=L,
+                                  **kw), device=dev)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRModel
 
@@ -560,6 +583,9 @@ def build_parser():
         p.add_argument("--pooling", default="sum", choices=("sum", "mean"),
                        help="pooling of a field's entries under "
                             "--layout field")
+        p.add_argument("--cross-layers", type=int, default=3,
+                       help="dcn: number of cross layers, 1..8 (predict: "
+                            "the checkpoint's)")
         p.add_argument("--device", default=None)
         p.add_argument("--seed", type=int, default=1234)
         p.add_argument("--save", default=None)

@@ -4,6 +4,7 @@ from .fwfm import FwFMModel, FwFMTrainer, FwFMHyper
 from .nfm import NFMModel, NFMTrainer, NFMHyper
 from .wide_deep import WideDeepModel, WideDeepTrainer, WideDeepHyper
 from .deepfm import DeepFMModel, DeepFMTrainer, DeepFMHyper
+from .dcn import DCNModel, DCNTrainer, DCNHyper
 from .mlp import MLP, DenseLayer
 from .gbm import GBMModel, GBMHyper
 from .gmm import GMMModel, GMMHyper
@@ -22,6 +23,7 @@ __all__ = [
     "NFMModel", "NFMTrainer", "NFMHyper",
     "WideDeepModel", "WideDeepTrainer", "WideDeepHyper",
     "DeepFMModel", "DeepFMTrainer", "DeepFMHyper",
+    "DCNModel", "DCNTrainer", "DCNHyper",
     "MLP", "DenseLayer",
     "GBMModel", "GBMHyper",
     "GMMModel", "GMMHyper",

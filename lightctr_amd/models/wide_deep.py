@@ -102,6 +102,10 @@ class WideDeepModel(BagLayout):
         out.view(B * nf, K).index_add_(0, flat_idx[keep], emb[keep])
         return out
 
+    def _score(self, wide, deep_in, train):
+        """pred [B] from the wide term and the concat row (DCN adds to it)"""
+        return wide + self.mlp.forward(deep_in, train=train)[:, 0]
+
     def _forward_gpu(self, row_ptr, fids, vals, train=True, fields=None):
         ops = require_hip_ops()
         wide = ops.wide_forward(row_ptr, fids, vals, self.W)
@@ -112,8 +116,7 @@ class WideDeepModel(BagLayout):
         else:
             deep_in = ops.embed_gather(row_ptr, fids, vals, self.E,
                                        self.h.num_fields)
-        deep = self.mlp.forward(deep_in, train=train)
-        return wide + deep[:, 0], wide
+        return self._score(wide, deep_in, train), wide
 
     def _forward_cpu(self, row_ptr, fids, vals, train=True, fields=None):
         B = row_ptr.numel() - 1
@@ -126,8 +129,7 @@ class WideDeepModel(BagLayout):
                                      self.h.num_fields, self.h.pooling)
         else:
             deep_in = self._gather_cpu(row_ptr, fids, vals)
-        deep = self.mlp.forward(deep_in, train=train)
-        return wide + deep[:, 0], wide
+        return self._score(wide, deep_in, train), wide
 
     def predict_proba(self, row_ptr, fids, vals, fields=None):
         fwd = self._forward_gpu if self._gpu else self._forward_cpu
@@ -145,38 +147,50 @@ class WideDeepModel(BagLayout):
                                            fields=fields)
             loss, dpred = ops.logloss_grad(pred, labels, scale)
             dDeep = self.mlp.backward(dpred.unsqueeze(1))  # [B, nf*K]
-            if fields is not None:
-                gw, gv = ops.embed_bag_backward_emit(
-                    row_ptr, fields, vals, dDeep.contiguous(), dpred,
-                    self.h.num_fields, self.h.k, self._pool)
-            else:
-                gw, gv = ops.embed_backward_emit(row_ptr, vals,
-                                                 dDeep.contiguous(), dpred,
-                                                 self.h.num_fields, self.h.k)
-            sorted_fids, perm = sort_ids(fids, self.h.num_features)
-            ops.fm_sorted_apply(sorted_fids, perm, gw, gv, self.gradW,
-                                self.gradE, self.touched)
-            self.count.zero_()
-            ops.bitmap_compact(self.touched, self.uniq, self.count)
-            live = self.uniq[: min(self.uniq.numel(), fids.numel())]
-            if self.h.optimizer == "ftrl":
-                ops.fm_ftrl_apply(live, self.count, self.W, self.E,
-                                  self.zW, self.nW, self.zE, self.nE,
-                                  self.gradW, self.gradE, self.h.ftrl_alpha,
-                                  self.h.ftrl_beta, self.h.ftrl_l1,
-                                  self.h.ftrl_l2,
-                                  1 if self.h.ftrl_v == "adagrad" else 0,
-                                  self.h.lr, self.h.eps, self.h.l2)
-            else:
-                ops.fm_adagrad_apply(live, self.count, self.W, self.E,
-                                     self.nW, self.nE, self.gradW, self.gradE,
-                                     self.h.lr, self.h.eps, self.h.l2)
+            self._sparse_step_gpu(row_ptr, fids, vals, fields, dDeep, dpred)
             self.mlp.apply_grads()
             return loss
         # CPU oracle
         pred, wide = self._forward_cpu(row_ptr, fids, vals, fields=fields)
         loss, dpred = fm_ref.logloss_grad_ref(pred, labels, scale)
         dDeep = self.mlp.backward(dpred.unsqueeze(1))
+        self._sparse_step_cpu(row_ptr, fids, vals, fields, dDeep, dpred)
+        self.mlp.apply_grads()
+        return loss
+
+    def _sparse_step_gpu(self, row_ptr, fids, vals, fields, dDeep, dpred):
+        """emit, sort, apply and the fused sparse optimizer for W and E,
+        from the concat's gradient dDeep [B, nf*K] and dpred [B]"""
+        ops = require_hip_ops()
+        if fields is not None:
+            gw, gv = ops.embed_bag_backward_emit(
+                row_ptr, fields, vals, dDeep.contiguous(), dpred,
+                self.h.num_fields, self.h.k, self._pool)
+        else:
+            gw, gv = ops.embed_backward_emit(row_ptr, vals,
+                                             dDeep.contiguous(), dpred,
+                                             self.h.num_fields, self.h.k)
+        sorted_fids, perm = sort_ids(fids, self.h.num_features)
+        ops.fm_sorted_apply(sorted_fids, perm, gw, gv, self.gradW,
+                            self.gradE, self.touched)
+        self.count.zero_()
+        ops.bitmap_compact(self.touched, self.uniq, self.count)
+        live = self.uniq[: min(self.uniq.numel(), fids.numel())]
+        if self.h.optimizer == "ftrl":
+            ops.fm_ftrl_apply(live, self.count, self.W, self.E,
+                              self.zW, self.nW, self.zE, self.nE,
+                              self.gradW, self.gradE, self.h.ftrl_alpha,
+                              self.h.ftrl_beta, self.h.ftrl_l1,
+                              self.h.ftrl_l2,
+                              1 if self.h.ftrl_v == "adagrad" else 0,
+                              self.h.lr, self.h.eps, self.h.l2)
+        else:
+            ops.fm_adagrad_apply(live, self.count, self.W, self.E,
+                                 self.nW, self.nE, self.gradW, self.gradE,
+                                 self.h.lr, self.h.eps, self.h.l2)
+
+    def _sparse_step_cpu(self, row_ptr, fids, vals, fields, dDeep, dpred):
+        B = row_ptr.numel() - 1
         rp = row_ptr.long()
         row_idx = torch.repeat_interleave(
             torch.arange(B), rp[1:] - rp[:-1])
@@ -207,8 +221,6 @@ class WideDeepModel(BagLayout):
             fm_ref.adagrad_apply_ref(uniq, self.W, self.E, self.nW, self.nE,
                                      self.gradW, self.gradE, self.h.lr,
                                      self.h.eps, self.h.l2)
-        self.mlp.apply_grads()
-        return loss
 
     def state_dict(self):
         return {"W": self.W, "E": self.E, "nW": self.nW, "nE": self.nE,

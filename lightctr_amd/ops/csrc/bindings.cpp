@@ -1981,6 +1981,110 @@ std::vector<at::Tensor> fwfm_backward_emit(at::Tensor row_ptr,
   return {gw, gv, dR};
 }
 
+// ---- Deep & Cross: the cross term on the concat row ----
+
+// Shared argument checks of the DCN bindings: Wc [L, d], u [d], 1 <= L <= 8,
+// d % 4 == 0 (vector accesses), w' within the device's LDS. Returns L.
+int check_dcn_params(const at::Tensor& Wc, const at::Tensor& u,
+                     const char* op) {
+  check_cuda_f32(Wc, "Wc");
+  CHK(Wc.dim() == 2, op, ": Wc must be [L, d]");
+  const int64_t L = Wc.size(0), d = Wc.size(1);
+  CHK(L >= 1 && L <= 8, op, ": 1 <= cross layers <= 8, got ", L);
+  CHK(d >= 4 && d % 4 == 0 && d <= (1 << 20), op,
+      ": d must be a multiple of 4 in [4, 2^20], got ", d);
+  check_f32_n(u, d, "u");
+  CHK(u.dim() == 1, op, ": u must be [d]");
+  const long need = lightctr::dcn_cross_lds_bytes((int)L, (int)d);
+  const long have = lightctr::ffm_max_lds_per_block();
+  CHK(need <= have, op, ": L=", L, ", d=", d, " needs ", need,
+      " bytes of LDS per block, the device gives ", have);
+  CHK((uintptr_t)Wc.data_ptr() % 16 == 0 && (uintptr_t)u.data_ptr() % 16 == 0,
+      op, ": Wc and u must be 16-byte aligned");
+  return (int)L;
+}
+
+// x0 bf16 [B, d]; returns B
+int check_dcn_x0(const at::Tensor& x0, int64_t d, const char* op) {
+  CHK(x0.is_cuda(), "x0 must be on GPU");
+  CHK(x0.scalar_type() == at::kBFloat16, op, ": x0 must be bf16");
+  CHK(x0.is_contiguous(), "x0 must be contiguous");
+  CHK(x0.dim() == 2 && x0.size(1) == d, op, ": x0 must be [B, ", d, "]");
+  CHK((uintptr_t)x0.data_ptr() % 8 == 0, op, ": x0 must be 8-byte aligned");
+  CHK(x0.size(0) < (1 << 24), op, ": B must be below 2^24");
+  return (int)x0.size(0);
+}
+
+// (C [L+1, d], q [L+1]): the batch-independent part, once per step
+std::vector<at::Tensor> dcn_cross_prep(at::Tensor Wc, at::Tensor bc,
+                                       at::Tensor u) {
+  const int L = check_dcn_params(Wc, u, "dcn_cross_prep");
+  const int d = (int)Wc.size(1);
+  check_f32_n(bc, (int64_t)L * d, "bc");
+  CHK(bc.dim() == 2 && bc.size(0) == L, "dcn_cross_prep: bc must be [L, d]");
+  auto C = at::empty({L + 1, d}, Wc.options());
+  auto q = at::empty({L + 1}, Wc.options());
+  lightctr::dcn_cross_prep_launch(Wc.data_ptr<float>(), bc.data_ptr<float>(),
+                                  u.data_ptr<float>(), C.data_ptr<float>(),
+                                  q.data_ptr<float>(), L, d, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {C, q};
+}
+
+// (cross [B], P [B, L+1]): one pass over x0
+std::vector<at::Tensor> dcn_cross_forward(at::Tensor x0, at::Tensor Wc,
+                                          at::Tensor u, at::Tensor q) {
+  const int L = check_dcn_params(Wc, u, "dcn_cross_forward");
+  const int d = (int)Wc.size(1);
+  const int B = check_dcn_x0(x0, d, "dcn_cross_forward");
+  check_f32_n(q, L + 1, "q");
+  auto cross = at::empty({B}, Wc.options());
+  auto P = at::empty({B, L + 1}, Wc.options());
+  if (B == 0) return {cross, P};  // nothing is launched
+  lightctr::dcn_cross_forward_launch(
+      x0.data_ptr(), Wc.data_ptr<float>(), u.data_ptr<float>(),
+      q.data_ptr<float>(), cross.data_ptr<float>(), P.data_ptr<float>(), L, d,
+      B, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {cross, P};
+}
+
+// (dWc [L, d], dbc [L, d], du [d]); dDeep [B, d] += dx0 in place
+std::vector<at::Tensor> dcn_cross_backward(at::Tensor x0, at::Tensor P,
+                                           at::Tensor Wc, at::Tensor u,
+                                           at::Tensor q, at::Tensor C,
+                                           at::Tensor dpred,
+                                           at::Tensor dDeep) {
+  const int L = check_dcn_params(Wc, u, "dcn_cross_backward");
+  const int d = (int)Wc.size(1);
+  const int B = check_dcn_x0(x0, d, "dcn_cross_backward");
+  check_f32_n(q, L + 1, "q");
+  check_f32_n(C, (int64_t)(L + 1) * d, "C");
+  check_f32_n(P, (int64_t)B * (L + 1), "P");
+  check_f32_n(dpred, B, "dpred");
+  check_f32_n(dDeep, (int64_t)B * d, "dDeep");
+  CHK(dDeep.dim() == 2 && dDeep.size(1) == d,
+      "dcn_cross_backward: dDeep must be [B, ", d, "]");
+  CHK((uintptr_t)dDeep.data_ptr() % 8 == 0,
+      "dcn_cross_backward: dDeep must be 8-byte aligned");
+  const int nchunks = lightctr::dcn_cross_backward_chunks(B);
+  CHK(nchunks <= 65535, "dcn_cross_backward: batch too large");
+  auto dWc = at::empty({L, d}, Wc.options());
+  auto dbc = at::empty({L, d}, Wc.options());
+  auto du = at::empty({d}, Wc.options());
+  auto partG = at::empty({nchunks, L + 1, d}, Wc.options());
+  auto partE = at::empty({nchunks, L + 1}, Wc.options());
+  lightctr::dcn_cross_backward_launch(
+      x0.data_ptr(), P.data_ptr<float>(), Wc.data_ptr<float>(),
+      u.data_ptr<float>(), q.data_ptr<float>(), C.data_ptr<float>(),
+      dpred.data_ptr<float>(), dDeep.data_ptr<float>(),
+      partG.data_ptr<float>(), partE.data_ptr<float>(),
+      dWc.data_ptr<float>(), dbc.data_ptr<float>(), du.data_ptr<float>(), L,
+      d, B, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {dWc, dbc, du};
+}
+
 // ---- native data loader ----
 // Fast single-pass libffm parser ("label field:fid:val" per line) —
 // native equivalent of the reference's C++ loader
@@ -2577,6 +2681,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fwfm_lds_bytes", &lightctr::fwfm_lds_bytes,
         "dynamic LDS per block the FwFM kernels need", py::arg("nf"),
         py::arg("K"));
+  m.def("dcn_cross_prep", &dcn_cross_prep,
+        "DCN cross term, batch-independent part: (C [L+1, d], q [L+1])");
+  m.def("dcn_cross_forward", &dcn_cross_forward,
+        "DCN cross term on the bf16 concat: (cross [B], P [B, L+1])");
+  m.def("dcn_cross_backward", &dcn_cross_backward,
+        "DCN cross backward, dDeep += dx0 in place: (dWc, dbc, du)");
+  m.def("dcn_cross_lds_bytes", &lightctr::dcn_cross_lds_bytes,
+        "dynamic LDS per block the DCN cross forward needs", py::arg("L"),
+        py::arg("d"));
+  m.def("dcn_cross_backward_rows", &lightctr::dcn_cross_backward_rows,
+        "rows per block (and per partial) of the DCN cross backward");
   m.def("wide_forward", &wide_forward, "LR wide forward sum");
   m.def("w2v_negsample_step", &w2v_negsample_step,
         "fused CBOW negative-sampling train step (Hogwild)");

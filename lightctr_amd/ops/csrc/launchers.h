@@ -352,6 +352,24 @@ void fwfm_backward_emit_launch(const int* row_ptr, const int* fields,
                                float* partial, float* dR, int nf, int B,
                                int K, ihipStream_t* stream);
 
+// --- dcn_kernels.hip (x0: bf16 [B, d]; 1 <= L <= 8, d % 4 == 0) ---
+long dcn_cross_lds_bytes(int L, int d);
+int dcn_cross_backward_rows();
+int dcn_cross_backward_chunks(int B);
+void dcn_cross_prep_launch(const float* Wc, const float* bc, const float* u,
+                           float* C, float* q, int L, int d,
+                           ihipStream_t* stream);
+void dcn_cross_forward_launch(const void* x0, const float* Wc, const float* u,
+                              const float* q, float* cross, float* P, int L,
+                              int d, int B, ihipStream_t* stream);
+void dcn_cross_backward_launch(const void* x0, const float* P,
+                               const float* Wc, const float* u,
+                               const float* q, const float* C,
+                               const float* dpred, float* dDeep, float* partG,
+                               float* partE, float* dWc, float* dbc,
+                               float* du, int L, int d, int B,
+                               ihipStream_t* stream);
+
 // --- codec_kernels.hip ---
 void quantile_encode_launch(const float* x, unsigned char* code,
                             const float* table, int levels, long n,
