@@ -11,6 +11,8 @@ command:
         (field-weighted FM; num_fields comes from the data)
     python -m lightctr_amd.cli train|predict --model dcn --cross-layers 3 ...
         (Deep & Cross; --layout / --pooling as for widedeep)
+    python -m lightctr_amd.cli train|predict --model dcn2 --cross-layers 3 \\
+        --cross-rank 64 ...       (DCN-v2, low-rank matrix cross layers)
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
     python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
         --data dense.csv ...      (dense rows; served by the compiled forest)
@@ -53,7 +55,7 @@ def _load_data(args):
 def cmd_train(args) -> int:
     dev = _device(args)
     if args.model not in ("fm", "ffm", "fwfm", "nfm", "widedeep", "deepfm",
-                          "dcn", "lr"):
+                          "dcn", "dcn2", "lr"):
         # the rest of the zoo reads dense / text data, not libffm
         return _train_other(args, dev)
     ds = _load_data(args)
@@ -123,6 +125,18 @@ def cmd_train(args) -> int:
                                      cross_layers=args.cross_layers),
                         device=dev, batch_size=args.batch,
                         epochs=args.epochs)
+    elif args.model == "dcn2":
+        from .models.dcn2 import DCNv2Hyper, DCNv2Trainer
+
+        tr = DCNv2Trainer(ds, DCNv2Hyper(num_features=F,
+                                         num_fields=ds.num_fields, k=args.k,
+                                         optimizer=args.optimizer, lr=args.lr,
+                                         layout=args.layout,
+                                         pooling=args.pooling,
+                                         cross_layers=args.cross_layers,
+                                         cross_rank=args.cross_rank),
+                          device=dev, batch_size=args.batch,
+                          epochs=args.epochs)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRTrainer
 
@@ -489,6 +503,19 @@ def cmd_predict(args) -> int:
         model = DCNModel(DCNHyper(num_features=F, k=args.k,
                                   optimizer=args.optimizer, cross_layers=L,
                                   **kw), device=dev)
+    elif args.model == "dcn2":
+        from .models.dcn2 import DCNv2Hyper, DCNv2Model
+
+        # U and V are [cross_layers, nf*k, cross_rank]: the checkpoint's
+        # depth and rank where it has them
+        ckpt, kw = _concat_setup(args, ds, dev)
+        hyper = (ckpt or {}).get("hyper", {})
+        model = DCNv2Model(
+            DCNv2Hyper(num_features=F, k=args.k, optimizer=args.optimizer,
+                       cross_layers=hyper.get("cross_layers",
+                                              args.cross_layers),
+                       cross_rank=hyper.get("cross_rank", args.cross_rank),
+                       **kw), device=dev)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRModel
 
@@ -584,8 +611,12 @@ def build_parser():
                        help="pooling of a field's entries under "
                             "--layout field")
         p.add_argument("--cross-layers", type=int, default=3,
-                       help="dcn: number of cross layers, 1..8 (predict: "
-                            "the checkpoint's)")
+                       help="dcn / dcn2: number of cross layers, 1..8 "
+                            "(predict: the checkpoint's)")
+        p.add_argument("--cross-rank", type=int, default=64,
+                       help="dcn2: rank of a cross layer's matrix, a "
+                            "multiple of 16 in 16..128 (predict: the "
+                            "checkpoint's)")
         p.add_argument("--device", default=None)
         p.add_argument("--seed", type=int, default=1234)
         p.add_argument("--save", default=None)

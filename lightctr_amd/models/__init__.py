@@ -5,6 +5,7 @@ from .nfm import NFMModel, NFMTrainer, NFMHyper
 from .wide_deep import WideDeepModel, WideDeepTrainer, WideDeepHyper
 from .deepfm import DeepFMModel, DeepFMTrainer, DeepFMHyper
 from .dcn import DCNModel, DCNTrainer, DCNHyper
+from .dcn2 import DCNv2Model, DCNv2Trainer, DCNv2Hyper
 from .mlp import MLP, DenseLayer
 from .gbm import GBMModel, GBMHyper
 from .gmm import GMMModel, GMMHyper
@@ -24,6 +25,7 @@ __all__ = [
     "WideDeepModel", "WideDeepTrainer", "WideDeepHyper",
     "DeepFMModel", "DeepFMTrainer", "DeepFMHyper",
     "DCNModel", "DCNTrainer", "DCNHyper",
+    "DCNv2Model", "DCNv2Trainer", "DCNv2Hyper",
     "MLP", "DenseLayer",
     "GBMModel", "GBMHyper",
     "GMMModel", "GMMHyper",

@@ -2085,6 +2085,120 @@ std::vector<at::Tensor> dcn_cross_backward(at::Tensor x0, at::Tensor P,
   return {dWc, dbc, du};
 }
 
+// ---- DCN-v2: low-rank matrix cross layers on the concat row ----
+
+// a bf16 mirror of the cross weights: [L, a, b], 16-byte aligned
+void check_dcn2_mirror(const at::Tensor& t, int64_t L, int64_t a, int64_t b,
+                       const char* op, const char* name) {
+  CHK(t.is_cuda(), name, " must be on GPU");
+  CHK(t.scalar_type() == at::kBFloat16, op, ": ", name, " must be bf16");
+  CHK(t.is_contiguous(), name, " must be contiguous");
+  CHK(t.dim() == 3 && t.size(0) == L && t.size(1) == a && t.size(2) == b, op,
+      ": ", name, " must be [", L, ", ", a, ", ", b, "]");
+  CHK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+      " must be 16-byte aligned");
+}
+
+struct Dcn2Dims {
+  int L, d, r, B;
+};
+
+// Shared argument checks of the DCN-v2 bindings: Ubf [L, d, r], bc [L, d],
+// u [d], x0 bf16 [B, d]; the served range and the device's LDS.
+Dcn2Dims check_dcn2_args(const at::Tensor& x0, const at::Tensor& Ubf,
+                         const at::Tensor& bc, const at::Tensor& u,
+                         const char* op) {
+  CHK(Ubf.dim() == 3, op, ": Ubf must be [L, d, r]");
+  const int64_t L = Ubf.size(0), d = Ubf.size(1), r = Ubf.size(2);
+  CHK(L >= 1 && L <= 8, op, ": 1 <= cross layers <= 8, got ", L);
+  CHK(d >= 4 && d % 4 == 0 && d <= 1024, op,
+      ": d must be a multiple of 4 in [4, 1024], got ", d);
+  CHK(r >= 16 && r % 16 == 0 && r <= 128, op,
+      ": the rank must be a multiple of 16 in [16, 128], got ", r);
+  check_dcn2_mirror(Ubf, L, d, r, op, "Ubf");
+  const long need = lightctr::dcn2_cross_lds_bytes((int)L, (int)d, (int)r);
+  const long have = lightctr::ffm_max_lds_per_block();
+  CHK(need <= have, op, ": L=", L, ", d=", d, ", r=", r, " needs ", need,
+      " bytes of LDS per block, the device gives ", have);
+  check_f32_n(bc, L * d, "bc");
+  CHK(bc.dim() == 2 && bc.size(0) == L, op, ": bc must be [L, d]");
+  check_f32_n(u, d, "u");
+  CHK(u.dim() == 1, op, ": u must be [d]");
+  const int B = check_dcn_x0(x0, d, op);
+  return {(int)L, (int)d, (int)r, B};
+}
+
+void check_dcn2_saved(const at::Tensor& t, int64_t L, int64_t B, int64_t w,
+                      const char* op, const char* name) {
+  CHK(t.is_cuda() && t.is_contiguous(), name,
+      " must be a contiguous GPU tensor");
+  CHK(t.scalar_type() == at::kBFloat16, op, ": ", name, " must be bf16");
+  CHK(t.dim() == 3 && t.size(0) == L && t.size(1) == B && t.size(2) == w, op,
+      ": ", name, " must be [", L, ", ", B, ", ", w, "]");
+  CHK((uintptr_t)t.data_ptr() % 8 == 0, op, ": ", name,
+      " must be 8-byte aligned");
+}
+
+// cross [B]; with save also X [L, B, d] (x_1 .. x_L) and T [L, B, r]
+std::vector<at::Tensor> dcn2_cross_forward(at::Tensor x0, at::Tensor Ubf,
+                                           at::Tensor Vtbf, at::Tensor bc,
+                                           at::Tensor u, bool save) {
+  const char* op = "dcn2_cross_forward";
+  const Dcn2Dims s = check_dcn2_args(x0, Ubf, bc, u, op);
+  check_dcn2_mirror(Vtbf, s.L, s.r, s.d, op, "Vtbf");
+  auto cross = at::empty({s.B}, bc.options());
+  at::Tensor X, T;
+  if (save) {
+    X = at::empty({s.L, s.B, s.d}, x0.options());
+    T = at::empty({s.L, s.B, s.r}, x0.options());
+  }
+  if (s.B > 0) {
+    lightctr::dcn2_cross_forward_launch(
+        x0.data_ptr(), Ubf.data_ptr(), Vtbf.data_ptr(), bc.data_ptr<float>(),
+        u.data_ptr<float>(), cross.data_ptr<float>(),
+        save ? X.data_ptr() : nullptr, save ? T.data_ptr() : nullptr, save,
+        s.L, s.d, s.r, s.B, cur_stream());
+    C10_CUDA_KERNEL_LAUNCH_CHECK();
+  }
+  if (save) return {cross, X, T};
+  return {cross};
+}
+
+// (G [L, B, d], S [L, B, r], dbc [L, d], du [d]); dDeep [B, d] += dx0
+std::vector<at::Tensor> dcn2_cross_backward(at::Tensor x0, at::Tensor X,
+                                            at::Tensor T, at::Tensor Ubf,
+                                            at::Tensor Utbf, at::Tensor Vbf,
+                                            at::Tensor bc, at::Tensor u,
+                                            at::Tensor dpred,
+                                            at::Tensor dDeep) {
+  const char* op = "dcn2_cross_backward";
+  const Dcn2Dims s = check_dcn2_args(x0, Ubf, bc, u, op);
+  check_dcn2_mirror(Utbf, s.L, s.r, s.d, op, "Utbf");
+  check_dcn2_mirror(Vbf, s.L, s.d, s.r, op, "Vbf");
+  check_dcn2_saved(X, s.L, s.B, s.d, op, "X");
+  check_dcn2_saved(T, s.L, s.B, s.r, op, "T");
+  check_f32_n(dpred, s.B, "dpred");
+  check_f32_n(dDeep, (int64_t)s.B * s.d, "dDeep");
+  CHK(dDeep.dim() == 2 && dDeep.size(1) == s.d, op, ": dDeep must be [B, ",
+      s.d, "]");
+  auto G = at::empty({s.L, s.B, s.d}, x0.options());
+  auto S = at::empty({s.L, s.B, s.r}, x0.options());
+  auto dbc = at::empty({s.L, s.d}, bc.options());
+  auto du = at::empty({s.d}, bc.options());
+  auto part = at::empty(
+      {lightctr::dcn2_cross_backward_blocks(s.B), s.L + 1, s.d},
+      bc.options());
+  lightctr::dcn2_cross_backward_launch(
+      x0.data_ptr(), X.data_ptr(), T.data_ptr(), Ubf.data_ptr(),
+      Utbf.data_ptr(), Vbf.data_ptr(), bc.data_ptr<float>(),
+      u.data_ptr<float>(), dpred.data_ptr<float>(), dDeep.data_ptr<float>(),
+      G.data_ptr(), S.data_ptr(), part.data_ptr<float>(),
+      dbc.data_ptr<float>(), du.data_ptr<float>(), s.L, s.d, s.r, s.B,
+      cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {G, S, dbc, du};
+}
+
 // ---- native data loader ----
 // Fast single-pass libffm parser ("label field:fid:val" per line) —
 // native equivalent of the reference's C++ loader
@@ -2692,6 +2806,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("d"));
   m.def("dcn_cross_backward_rows", &lightctr::dcn_cross_backward_rows,
         "rows per block (and per partial) of the DCN cross backward");
+  m.def("dcn2_cross_forward", &dcn2_cross_forward,
+        "DCN-v2 cross term on the bf16 concat, all layers in one launch: "
+        "(cross [B]) or, with save, (cross, X [L, B, d], T [L, B, r])",
+        py::arg("x0"), py::arg("Ubf"), py::arg("Vtbf"), py::arg("bc"),
+        py::arg("u"), py::arg("save"));
+  m.def("dcn2_cross_backward", &dcn2_cross_backward,
+        "DCN-v2 cross backward, dDeep += dx0 in place: (G [L, B, d], "
+        "S [L, B, r], dbc, du)");
+  m.def("dcn2_cross_lds_bytes", &lightctr::dcn2_cross_lds_bytes,
+        "dynamic LDS per block the DCN-v2 cross kernels need", py::arg("L"),
+        py::arg("d"), py::arg("r"));
+  m.def("dcn2_cross_tile_rows", &lightctr::dcn2_cross_tile_rows,
+        "rows per block tile of the DCN-v2 cross kernels");
   m.def("wide_forward", &wide_forward, "LR wide forward sum");
   m.def("w2v_negsample_step", &w2v_negsample_step,
         "fused CBOW negative-sampling train step (Hogwild)");

@@ -370,6 +370,25 @@ void dcn_cross_backward_launch(const void* x0, const float* P,
                                float* du, int L, int d, int B,
                                ihipStream_t* stream);
 
+// --- dcn2_kernels.hip (x0: bf16 [B, d]; Ubf, Vbf: bf16 [L, d, r]; Utbf,
+// Vtbf: bf16 [L, r, d]; 1 <= L <= 8, d % 4 == 0, d <= 1024, r % 16 == 0,
+// r <= 128) ---
+long dcn2_cross_lds_bytes(int L, int d, int r);
+int dcn2_cross_tile_rows();
+int dcn2_cross_backward_blocks(int B);
+void dcn2_cross_forward_launch(const void* x0, const void* Ubf,
+                               const void* Vtbf, const float* bc,
+                               const float* u, float* cross, void* X, void* T,
+                               bool save, int L, int d, int r, int B,
+                               ihipStream_t* stream);
+void dcn2_cross_backward_launch(const void* x0, const void* X, const void* T,
+                                const void* Ubf, const void* Utbf,
+                                const void* Vbf, const float* bc,
+                                const float* u, const float* dpred,
+                                float* dDeep, void* G, void* S, float* part,
+                                float* dbc, float* du, int L, int d, int r,
+                                int B, ihipStream_t* stream);
+
 // --- codec_kernels.hip ---
 void quantile_encode_launch(const float* x, unsigned char* code,
                             const float* table, int levels, long n,
