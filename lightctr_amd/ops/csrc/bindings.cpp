@@ -548,6 +548,18 @@ void fm_segment_tile_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
   const long B = dpred.numel();
   CHK(sumVX.numel() == B * K, "sumVX must be [B, K]");
   CHK(nnz == 0 || B >= 1, "entries need rows");
+  // the kernel moves four factors of a row as one float4
+  CHK(K % 4 == 0, "K must be a multiple of 4");
+  auto check_aligned16 = [](const at::Tensor& t, const char* name) {
+    CHK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+        " must be 16-byte aligned (its rows are read as float4); a view "
+        "that starts inside a float4 is not");
+  };
+  check_aligned16(sumVX, "sumVX");
+  check_aligned16(V, "V");
+  check_aligned16(nV, "nV");
+  check_aligned16(gradV, "gradV");
+  if (zV.has_value()) check_aligned16(*zV, "zV");
   lightctr::fm_segment_tile_launch(
       sorted_fids.data_ptr<int>(), sorted_rec.data_ptr<int>(),
       sumVX.data_ptr<float>(), dpred.data_ptr<float>(), (int)B, (int)cap,
@@ -2666,7 +2678,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "entries per block of fm_segment_tile_rec");
   m.def("fm_segment_split", &lightctr::fm_segment_split,
         "longest unit one subgroup sums in fm_segment_tile_rec");
-  m.def("ffm_forward", &ffm_forward, "FFM pairwise forward (LDS-staged)");
+  m.def("fm_segment_threads", &lightctr::fm_segment_threads,
+        "threads per block of fm_segment_tile_rec (a unit takes K/4)");  m.def("ffm_forward", &ffm_forward, "FFM pairwise forward (LDS-staged)");
   m.def("ffm_forward_pp", &ffm_forward_pp, "lane-per-pair FFM forward");
   m.def("ffm_row_emit", &ffm_row_emit,
         "FFM per-row staged fp16 block emit -> (gw, gblocks)",

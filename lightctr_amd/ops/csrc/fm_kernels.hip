@@ -768,6 +768,19 @@ struct FmSrcGathered {
   }
 };
 
+// One entry's contribution to its fid's gradient, recomputed from d =
+// dpred[row], x, sv = sumVX[row, k] and the fid's old v = V[fid, k]. The one
+// place these expressions live: the list-fed and the tile reduce both call
+// them per (entry, k), so both are contracted the same way.
+__device__ __forceinline__ void fm_entry_grad_v(float d, float x, float sv,
+                                                float v, float& acc) {
+  acc += d * (sv - v * x) * x;
+}
+__device__ __forceinline__ void fm_entry_grad_w(float d, float x,
+                                                float& accw) {
+  accw += d * x;
+}
+
 // Recompute: the sort carried the forward's records {row, bits of x} as its
 // payload, so position e holds the entry's row and value directly (no perm,
 // no per-entry gradient buffer). The gathers go to sumVX (B*K floats, a few
@@ -794,8 +807,8 @@ struct FmSrcRecompute {
   __device__ __forceinline__ void add(Handle h, Data t, float v, float& acc,
                                       float& accw) const {
     const float x = __int_as_float(h.y);
-    acc += t.d * (t.sv - v * x) * x;
-    accw += t.d * x;
+    fm_entry_grad_v(t.d, x, t.sv, v, acc);
+    fm_entry_grad_w(t.d, x, accw);
   }
 };
 
@@ -946,10 +959,12 @@ __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
 //      piece cut once more at the multiples of SPLIT of the sorted position
 //      (CUT = min(CAP, SPLIT)), so it is at most SPLIT long; a list entry
 //      also says whether its unit starts a piece;
-//   3. every K-lane subgroup takes NF units per turn and issues all their
-//      row loads (V, and for a one-unit piece nV/W/nW/zW, plus the first
-//      entry's sumVX/dpred) together: the fids and records come from LDS, so
-//      the only dependent global level left is the gathers themselves.
+//   3. every subgroup of K/4 lanes takes one unit per turn; lane q owns the
+//      factors 4q..4q+3 and moves them as one float4, so a wave's load
+//      instruction covers 256/K units' rows. The subgroup issues all the
+//      unit's row loads (V, and for a one-unit piece nV/W/nW/zW, plus the
+//      first entry's sumVX/dpred) together: the fids and records come from
+//      LDS, so the only dependent global level left is the gathers themselves.
 //      A one-unit piece is finished on the spot as in the kernel above
 //      (whole: optimizer in place; partial: slabs + spill list), with the
 //      same per-entry expressions in the same order. A unit of a longer
@@ -964,38 +979,53 @@ __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
 // barrier, partial pieces never store (the spill apply, launched next, does).
 // Slots: a unit of a multi-unit piece either starts on a multiple of CUT
 // (slot 2c for cell c) or is its piece's first unit and reaches the end of
-// its cell (slot 2c + 1, at most one per cell): 2 * TILE / SPLIT slots.
+// its cell (slot 2c + 1, at most one per cell): 2 * TILE / SPLIT slots of
+// K/4 + 1 float4 (the factors, then accw). V, nV, zV, gradV and sumVX are
+// addressed as float4: the binding checks that they are 16-byte aligned.
+// D: entries per batch inside a unit (independent gathers in flight).
 // ---------------------------------------------------------------------------
 constexpr int kFmTilePieceBit = 1 << 30;  // list entry: unit starts a piece
 
-template <int K, int TILE, int SPLIT, int NF>
-__global__ __launch_bounds__(256) void fm_segment_tile_kernel(
+// the float4 arithmetic below stays four scalar operations per lane (no
+// v_pk_*_f32), the same instructions as the list-fed reduce's
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(                                     \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+
+template <int K, int NT, int TILE, int SPLIT, int D>
+__global__ __launch_bounds__(NT) void fm_segment_tile_kernel(
     const int* __restrict__ sorted_fids, const int2* __restrict__ rec,
     const float* __restrict__ sumVX, const float* __restrict__ dpred, int B,
     int cap, float* __restrict__ gradW, float* __restrict__ gradV,
     int* __restrict__ spill, int* __restrict__ spill_count, int spill_cap,
     int nnz, int opt_mode, float* __restrict__ V, FmOptArgs oa) {
-  constexpr int NT = 256;
+  constexpr int L = K / 4;  // lanes per unit
   constexpr int NW = NT / LCTR_WAVE;
   constexpr int ITEMS = TILE / NT;
-  constexpr int NSG = NT / K;  // subgroups per block
-  constexpr int D = 4;         // gathers in flight per lane inside a unit
+  constexpr int NSG = NT / L;  // subgroups per block
   constexpr int NSLOT = 2 * TILE / SPLIT;
+  constexpr int PS = L + 1;  // float4 per slot
+  static_assert(K % 4 == 0 && NT % LCTR_WAVE == 0, "lane layout");
   static_assert(TILE % NT == 0 && TILE % SPLIT == 0, "tile shape");
 
   __shared__ int s_fid[TILE + 2];  // [0] = fid before the tile, [n+1] after
   __shared__ int2 s_rec[TILE];
   __shared__ int s_unit[TILE + 1];
   __shared__ int s_multi[TILE / SPLIT];
-  __shared__ float s_part[NSLOT * (K + 1)];
+  __shared__ float4 s_part[NSLOT * PS];
   __shared__ int s_wave_tot[NW];
   __shared__ int s_nmulti;
 
   const int tid = threadIdx.x;
   const int lane = tid & (LCTR_WAVE - 1);
   const int wv = tid >> 6;
-  const int sg = tid / K;
-  const int k = tid % K;
+  const int sg = tid / L;
+  const int q = tid % L;
+  const float4* __restrict__ sumVX4 = (const float4*)sumVX;
+  float4* __restrict__ V4 = (float4*)V;
+  float4* __restrict__ nV4 = (float4*)oa.nV;
+  float4* __restrict__ zV4 = (float4*)oa.zV;
   const long t0 = (long)blockIdx.x * TILE;
   const int n = (int)min((long)TILE, (long)nnz - t0);
   if (n <= 0) return;
@@ -1074,103 +1104,124 @@ __global__ __launch_bounds__(256) void fm_segment_tile_kernel(
       if (spill_me && slot < spill_cap) spill[slot] = fid;  // clamp
     }
   };
-  auto gather = [&](int i, float& sv, float& d) {
+  auto gather = [&](int i, float4& sv, float& d) {
     // rows come from the forward kernel; the clamp only keeps a foreign
     // record buffer from reading outside sumVX / dpred
     const int row = min(max(s_rec[i].x, 0), B - 1);
-    sv = sumVX[(size_t)row * K + k];
+    sv = sumVX4[(size_t)row * L + q];
     d = dpred[row];
   };
-  auto add = [&](int i, float sv, float d, float v, float& acc,
-                 float& accw) {
+  auto add = [&](int i, const float4& sv, float d, const float4& v,
+                 float4& acc, float& accw) {
     const float x = __int_as_float(s_rec[i].y);
-    acc += d * (sv - v * x) * x;
-    accw += d * x;
+    fm_entry_grad_v(d, x, sv.x, v.x, acc.x);
+    fm_entry_grad_v(d, x, sv.y, v.y, acc.y);
+    fm_entry_grad_v(d, x, sv.z, v.z, acc.z);
+    fm_entry_grad_v(d, x, sv.w, v.w, acc.w);
+    fm_entry_grad_w(d, x, accw);
+  };
+  // the optimizer state of a whole piece's fid, loaded beside its V row
+  struct State {
+    float4 nv, z;
+    float w, nw, zw;
+  };
+  auto load_state = [&](bool whole, int fid) {
+    State s{make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f),
+            0.f, 0.f, 0.f};
+    if (whole) {
+      const size_t off = (size_t)fid * L + q;
+      s.nv = nV4[off];
+      if (opt_mode == 2) s.z = zV4[off];
+      if (q == 0) {
+        s.w = oa.W[fid];
+        s.nw = oa.nW[fid];
+        if (opt_mode != 1) s.zw = oa.zW[fid];
+      }
+    }
+    return s;
+  };
+  // a finished piece's sum `acc`/`accw` of fid: `whole` applies the optimizer
+  // to the fid's rows (v: the old V row, s: load_state), otherwise the sum
+  // goes to the slabs
+  auto finish = [&](bool whole, int fid, float4 v, const State& s,
+                    const float4& acc, float accw) {
+    const size_t off = (size_t)fid * L + q;
+    if (whole) {
+      float4 nv = s.nv, z = s.z;
+      fm_opt_step_v(opt_mode, v.x, nv.x, z.x, acc.x, oa);
+      fm_opt_step_v(opt_mode, v.y, nv.y, z.y, acc.y, oa);
+      fm_opt_step_v(opt_mode, v.z, nv.z, z.z, acc.z, oa);
+      fm_opt_step_v(opt_mode, v.w, nv.w, z.w, acc.w, oa);
+      if (opt_mode == 2) zV4[off] = z;
+      nV4[off] = nv;
+      V4[off] = v;
+      if (q == 0) {
+        float w = s.w, nw = s.nw, zw = s.zw;
+        fm_opt_step_w(opt_mode, w, nw, zw, accw, oa);
+        if (opt_mode != 1) oa.zW[fid] = zw;
+        oa.nW[fid] = nw;
+        oa.W[fid] = w;
+      }
+    } else {
+      float* g = gradV + (size_t)fid * K + 4 * q;
+      atomicAdd(g + 0, acc.x);
+      atomicAdd(g + 1, acc.y);
+      atomicAdd(g + 2, acc.z);
+      atomicAdd(g + 3, acc.w);
+      if (q == 0) atomicAdd(&gradW[fid], accw);
+    }
   };
 
   // -- 3. units ------------------------------------------------------------
-  for (int j0 = 0; j0 < nu; j0 += NSG * NF) {
-    int us[NF], ue[NF], fid[NF];
-    bool single[NF], first[NF], whole[NF], headp[NF];
-    float v[NF], nv[NF], z[NF], w[NF], nw[NF], zw[NF], sv0[NF], d0[NF];
+  for (int j0 = 0; j0 < nu; j0 += NSG) {
+    const int j = j0 + sg;
+    bool spill_me = false;
+    int fid = 0;
+    if (j < nu) {
+      const int a = s_unit[j], b = s_unit[j + 1];
+      const int us = a & (kFmTilePieceBit - 1);
+      const int ue = b & (kFmTilePieceBit - 1);
+      const bool first = (a & kFmTilePieceBit) != 0;
+      const bool single = first && (b & kFmTilePieceBit) != 0;
+      fid = s_fid[us + 1];
+      const float4 v = V4[(size_t)fid * L + q];
+      float4 sv0;
+      float d0;
+      gather(us, sv0, d0);
+      const bool headp = single && is_head(us);
+      const bool whole = headp && is_tail_before(ue, fid);
+      const State st = load_state(whole, fid);
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      float accw = 0.f;
+      for (int e = us + 1; e < ue; e += D) {
+        float4 sv[D];
+        float d[D];
 #pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const int j = j0 + f * NSG + sg;
-      us[f] = ue[f] = 0;
-      fid[f] = 0;
-      single[f] = first[f] = whole[f] = headp[f] = false;
-      v[f] = nv[f] = z[f] = w[f] = nw[f] = zw[f] = sv0[f] = d0[f] = 0.f;
-      if (j < nu) {
-        const int a = s_unit[j], b = s_unit[j + 1];
-        us[f] = a & (kFmTilePieceBit - 1);
-        ue[f] = b & (kFmTilePieceBit - 1);
-        first[f] = (a & kFmTilePieceBit) != 0;
-        single[f] = first[f] && (b & kFmTilePieceBit) != 0;
-        fid[f] = s_fid[us[f] + 1];
-        const size_t off = (size_t)fid[f] * K + k;
-        v[f] = V[off];
-        gather(us[f], sv0[f], d0[f]);
-        if (single[f]) {
-          headp[f] = is_head(us[f]);
-          whole[f] = headp[f] && is_tail_before(ue[f], fid[f]);
+        for (int u = 0; u < D; ++u) {
+          sv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+          d[u] = 0.f;
+          if (e + u < ue) gather(e + u, sv[u], d[u]);
         }
-        if (whole[f]) {
-          nv[f] = oa.nV[off];
-          if (opt_mode == 2) z[f] = oa.zV[off];
-          if (k == 0) {
-            w[f] = oa.W[fid[f]];
-            nw[f] = oa.nW[fid[f]];
-            if (opt_mode != 1) zw[f] = oa.zW[fid[f]];
-          }
+#pragma unroll
+        for (int u = 0; u < D; ++u)
+          if (e + u < ue) add(e + u, sv[u], d[u], v, acc, accw);
+      }
+      // the head entry last, as in fm_segment_apply_kernel
+      add(us, sv0, d0, v, acc, accw);
+      if (single) {
+        finish(whole, fid, v, st, acc, accw);
+        spill_me = !whole && headp && (q == 0);
+      } else {
+        const int c = us / SPLIT;
+        const int slot = 2 * c + ((us & (SPLIT - 1)) ? 1 : 0);
+        s_part[slot * PS + q] = acc;
+        if (q == 0) {
+          s_part[slot * PS + L].x = accw;
+          if (first) s_multi[atomicAdd(&s_nmulti, 1)] = j;
         }
       }
     }
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      bool spill_me = false;
-      if (ue[f] > us[f]) {
-        float acc = 0.f, accw = 0.f;
-        for (int e = us[f] + 1; e < ue[f]; e += D) {
-          float sv[D], d[D];
-#pragma unroll
-          for (int u = 0; u < D; ++u) {
-            sv[u] = d[u] = 0.f;
-            if (e + u < ue[f]) gather(e + u, sv[u], d[u]);
-          }
-#pragma unroll
-          for (int u = 0; u < D; ++u)
-            if (e + u < ue[f]) add(e + u, sv[u], d[u], v[f], acc, accw);
-        }
-        // the head entry last, as in fm_segment_apply_kernel
-        add(us[f], sv0[f], d0[f], v[f], acc, accw);
-        const size_t off = (size_t)fid[f] * K + k;
-        if (whole[f]) {
-          fm_opt_step_v(opt_mode, v[f], nv[f], z[f], acc, oa);
-          if (opt_mode == 2) oa.zV[off] = z[f];
-          oa.nV[off] = nv[f];
-          V[off] = v[f];
-          if (k == 0) {
-            fm_opt_step_w(opt_mode, w[f], nw[f], zw[f], accw, oa);
-            if (opt_mode != 1) oa.zW[fid[f]] = zw[f];
-            oa.nW[fid[f]] = nw[f];
-            oa.W[fid[f]] = w[f];
-          }
-        } else if (single[f]) {
-          atomicAdd(&gradV[off], acc);
-          if (k == 0) atomicAdd(&gradW[fid[f]], accw);
-          spill_me = headp[f] && (k == 0);
-        } else {
-          const int c = us[f] / SPLIT;
-          const int slot = 2 * c + ((us[f] & (SPLIT - 1)) ? 1 : 0);
-          s_part[slot * (K + 1) + k] = acc;
-          if (k == 0) {
-            s_part[slot * (K + 1) + K] = accw;
-            if (first[f]) s_multi[atomicAdd(&s_nmulti, 1)] = j0 + f * NSG + sg;
-          }
-        }
-      }
-      append_spill(spill_me, fid[f]);
-    }
+    append_spill(spill_me, fid);
   }
   __syncthreads();
 
@@ -1183,50 +1234,36 @@ __global__ __launch_bounds__(256) void fm_segment_tile_kernel(
       int j = s_multi[m0 + sg];
       const int ps = s_unit[j] & (kFmTilePieceBit - 1);
       fidm = s_fid[ps + 1];
-      const size_t off = (size_t)fidm * K + k;
       // the piece's end: the next list entry that starts a piece
       int j1 = j + 1;
       while (!(s_unit[j1] & kFmTilePieceBit)) ++j1;
       const int pe = s_unit[j1] & (kFmTilePieceBit - 1);
       const bool whole = is_head(ps) && is_tail_before(pe, fidm);
-      float v = 0.f, nv = 0.f, z = 0.f, w = 0.f, nw = 0.f, zw = 0.f;
-      if (whole) {
-        v = V[off];
-        nv = oa.nV[off];
-        if (opt_mode == 2) z = oa.zV[off];
-        if (k == 0) {
-          w = oa.W[fidm];
-          nw = oa.nW[fidm];
-          if (opt_mode != 1) zw = oa.zW[fidm];
-        }
-      }
-      float acc = 0.f, accw = 0.f;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (whole) v = V4[(size_t)fidm * L + q];
+      const State st = load_state(whole, fidm);
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      float accw = 0.f;
       for (; j < j1; ++j) {
         const int s = s_unit[j] & (kFmTilePieceBit - 1);
         const int slot = 2 * (s / SPLIT) + ((s & (SPLIT - 1)) ? 1 : 0);
-        acc += s_part[slot * (K + 1) + k];
-        accw += s_part[slot * (K + 1) + K];
+        const float4 p = s_part[slot * PS + q];
+        acc.x += p.x;
+        acc.y += p.y;
+        acc.z += p.z;
+        acc.w += p.w;
+        accw += s_part[slot * PS + L].x;
       }
-      if (whole) {
-        fm_opt_step_v(opt_mode, v, nv, z, acc, oa);
-        if (opt_mode == 2) oa.zV[off] = z;
-        oa.nV[off] = nv;
-        V[off] = v;
-        if (k == 0) {
-          fm_opt_step_w(opt_mode, w, nw, zw, accw, oa);
-          if (opt_mode != 1) oa.zW[fidm] = zw;
-          oa.nW[fidm] = nw;
-          oa.W[fidm] = w;
-        }
-      } else {
-        atomicAdd(&gradV[off], acc);
-        if (k == 0) atomicAdd(&gradW[fidm], accw);
-        spill_me = is_head(ps) && (k == 0);
-      }
+      finish(whole, fidm, v, st, acc, accw);
+      spill_me = !whole && is_head(ps) && (q == 0);
     }
     append_spill(spill_me, fidm);
   }
 }
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
 
 // ---------------------------------------------------------------------------
 // Bitmap -> unique-fid list compaction. One thread per 64-feature word;
@@ -1602,15 +1639,17 @@ void fm_segment_recompute_launch(
                     a, src, stream)));
 }
 
-// Shape of the tile reduce: entries per block, longest unit, units a
-// subgroup keeps in flight. Swept over {256, 512, 1024} x {16, 32, 64} x
-// {1, 2, 4} at the flagship shape (profiles/r5_01_fm_tile.txt): the smallest
-// tile wins (more blocks for the dispatcher to balance, 8 blocks per CU),
-// SPLIT 16 and 32 tie, and a second unit in flight buys nothing at TILE 256
-// (four in flight lose 5 %): occupancy beats lookahead here too.
-constexpr int kFmTile = 256;
-constexpr int kFmTileSplit = 32;
-constexpr int kFmTileFlight = 1;
+// Shape of the tile reduce: entries per block, longest unit, threads per
+// block, gathers in flight inside a unit. With K/4 lanes per unit, swept over
+// threads {64, 128, 256} at TILE 256 and 256 at TILE 512, SPLIT {8, 16, 32},
+// D {2, 4} at the flagship shape (profiles/r9_01_fm_tile_quad.txt): a block
+// has 4x the subgroups it had with K lanes per unit, so it wants more units:
+// TILE 512 beats every TILE 256 shape, and SPLIT 16 spreads a hot run over
+// twice the subgroups SPLIT 32 does. No scratch at any K.
+constexpr int kFmTile = 512;
+constexpr int kFmTileSplit = 16;
+constexpr int kFmTileThreads = 256;
+constexpr int kFmTileDepth = 4;
 
 struct FmTileArgs {
   const int* sorted_fids;
@@ -1627,13 +1666,13 @@ struct FmTileArgs {
   FmOptArgs oa;
 };
 
-template <int K, int TILE, int SPLIT, int NF>
+template <int K, int NT, int TILE, int SPLIT, int D>
 static void fm_segment_tile_launch_one(const FmTileArgs& a,
                                        hipStream_t stream) {
   // one block per tile: the count is known here, the dispatcher balances
   const int blocks = (int)(((long)a.nnz + TILE - 1) / TILE);
-  hipLaunchKernelGGL((fm_segment_tile_kernel<K, TILE, SPLIT, NF>),
-                     dim3(blocks), dim3(256), 0, stream, a.sorted_fids,
+  hipLaunchKernelGGL((fm_segment_tile_kernel<K, NT, TILE, SPLIT, D>),
+                     dim3(blocks), dim3(NT), 0, stream, a.sorted_fids,
                      (const int2*)a.rec, a.sumVX, a.dpred, a.B, a.cap, a.gradW,
                      a.gradV, a.spill, a.spill_count, a.spill_cap, a.nnz,
                      a.opt_mode, a.V, a.oa);
@@ -1641,6 +1680,7 @@ static void fm_segment_tile_launch_one(const FmTileArgs& a,
 
 int fm_segment_tile() { return kFmTile; }
 int fm_segment_split() { return kFmTileSplit; }
+int fm_segment_threads() { return kFmTileThreads; }
 
 void fm_segment_tile_launch(const int* sorted_fids, const int* rec,
                             const float* sumVX, const float* dpred, int B,
@@ -1655,8 +1695,9 @@ void fm_segment_tile_launch(const int* sorted_fids, const int* rec,
                      spill, spill_count, spill_cap, nnz, opt_mode, V,
                      FmOptArgs{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1,
                                q2}};
-  DISPATCH_K(K, (fm_segment_tile_launch_one<KC, kFmTile, kFmTileSplit,
-                                            kFmTileFlight>(a, stream)));
+  DISPATCH_K(K, (fm_segment_tile_launch_one<KC, kFmTileThreads, kFmTile,
+                                            kFmTileSplit, kFmTileDepth>(
+                    a, stream)));
 }
 
 void bitmap_compact_launch(unsigned long long* bitmap, int nwords,

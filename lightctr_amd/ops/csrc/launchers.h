@@ -61,6 +61,7 @@ void fm_segment_recompute_launch(
 // multiple of cap; no work list
 int fm_segment_tile();
 int fm_segment_split();
+int fm_segment_threads();
 void fm_segment_tile_launch(const int* sorted_fids, const int* rec,
                             const float* sumVX, const float* dpred, int B,
                             int cap, float* gradW, float* gradV, int* spill,

@@ -2,12 +2,13 @@
 hipGraph on the flagship batch pool, backward_mode="segment" (tile reduce)
 against "segment_list" (work list + per-piece reduce) in one process.
 
-The tile reduce's shape (entries per block, longest unit, units a subgroup
-keeps in flight) is a set of template parameters, kFmTile / kFmTileSplit /
-kFmTileFlight in fm_kernels.hip. A build that instantiates the other values
-behind a run-time selector (ops.fm_segment_tile_select(tile, split, flight),
-as was done for profiles/r5_01_fm_tile.txt) gets the whole grid swept; the
-shipped build has one instantiation, and then only segment_cap is swept.
+The tile reduce's shape (threads per block, entries per block, longest unit,
+gathers in flight inside a unit) is a set of template parameters,
+kFmTileThreads / kFmTile / kFmTileSplit / kFmTileDepth in fm_kernels.hip. A
+build that instantiates the other values behind a run-time selector
+(ops.fm_segment_tile_select(threads, tile, split, depth), as was done for
+profiles/r9_01_fm_tile_quad.txt) gets the whole grid swept; the shipped
+build has one instantiation, and then only segment_cap is swept.
 
     python tools/bench_fm_tile.py [--steps 2000] [--passes 2]
 """
@@ -24,10 +25,11 @@ from lightctr_amd.data.synthetic import SyntheticCriteo
 from lightctr_amd.models.fm import FMHyper, FMModel
 from lightctr_amd.ops._extension import require_hip_ops
 
-TILES = (256, 512, 1024)
-SPLITS = (16, 32, 64)
-FLIGHTS = (1, 2, 4)
-CAPS = (256, 512, 1024)
+# (threads, tile): tiles below 256 threads only at TILE 256
+BLOCKS = ((64, 256), (128, 256), (256, 256), (256, 512))
+SPLITS = (8, 16, 32)
+DEPTHS = (2, 4)
+CAPS = (256, 512)
 
 
 def graph_ms(model, pool, steps):
@@ -71,11 +73,14 @@ def main():
 
     select = getattr(ops, "fm_segment_tile_select", None)
     if select is None:
-        shapes = [(ops.fm_segment_tile(), ops.fm_segment_split(), None)]
-        print(f"# one tile shape built: TILE {shapes[0][0]} SPLIT "
-              f"{shapes[0][1]}; sweeping segment_cap only")
+        shapes = [(ops.fm_segment_threads(), ops.fm_segment_tile(),
+                   ops.fm_segment_split(), None)]
+        print(f"# one tile shape built: {shapes[0][0]} threads TILE "
+              f"{shapes[0][1]} SPLIT {shapes[0][2]}; sweeping segment_cap "
+              f"only")
     else:
-        shapes = [(t, s, f) for t in TILES for s in SPLITS for f in FLIGHTS]
+        shapes = [(nt, t, s, d) for nt, t in BLOCKS for s in SPLITS
+                  for d in DEPTHS]
     print(f"# step ms under hipGraph, {args.steps} steps, flagship pool")
     for p in range(args.passes):
         m.backward_mode = "segment_list"
@@ -85,16 +90,16 @@ def main():
             print(f"pass {p}: segment_list cap {cap:4d}  {ms:.4f} ms/step",
                   flush=True)
         m.backward_mode = "segment"
-        for tile, split, flight in shapes:
+        for nt, tile, split, depth in shapes:
             if select is not None:
-                select(tile, split, flight)
+                select(nt, tile, split, depth)
             for cap in CAPS:
                 if cap > tile:
                     continue
                 m.segment_cap = cap
                 ms = graph_ms(m, pool, args.steps)
-                print(f"pass {p}: segment TILE {tile:4d} SPLIT {split:2d} "
-                      f"flight {flight} cap {cap:4d}  {ms:.4f} ms/step",
+                print(f"pass {p}: segment NT {nt:3d} TILE {tile:4d} SPLIT "
+                      f"{split:2d} D {depth} cap {cap:4d}  {ms:.4f} ms/step",
                       flush=True)
 
 
