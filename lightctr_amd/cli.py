@@ -13,6 +13,8 @@ command:
         (Deep & Cross; --layout / --pooling as for widedeep)
     python -m lightctr_amd.cli train|predict --model dcn2 --cross-layers 3 \\
         --cross-rank 64 ...       (DCN-v2, low-rank matrix cross layers)
+    python -m lightctr_amd.cli train|predict --model xdeepfm --cin-layers 2 \\
+        --cin-maps 64 ...         (xDeepFM, compressed interaction network)
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
     python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
         --data dense.csv ...      (dense rows; served by the compiled forest)
@@ -55,7 +57,7 @@ def _load_data(args):
 def cmd_train(args) -> int:
     dev = _device(args)
     if args.model not in ("fm", "ffm", "fwfm", "nfm", "widedeep", "deepfm",
-                          "dcn", "dcn2", "lr"):
+                          "dcn", "dcn2", "xdeepfm", "lr"):
         # the rest of the zoo reads dense / text data, not libffm
         return _train_other(args, dev)
     ds = _load_data(args)
@@ -137,6 +139,19 @@ def cmd_train(args) -> int:
                                          cross_rank=args.cross_rank),
                           device=dev, batch_size=args.batch,
                           epochs=args.epochs)
+    elif args.model == "xdeepfm":
+        from .models.xdeepfm import XDeepFMHyper, XDeepFMTrainer
+
+        tr = XDeepFMTrainer(ds, XDeepFMHyper(num_features=F,
+                                             num_fields=ds.num_fields,
+                                             k=args.k,
+                                             optimizer=args.optimizer,
+                                             lr=args.lr, layout=args.layout,
+                                             pooling=args.pooling,
+                                             cin_layers=args.cin_layers,
+                                             cin_maps=args.cin_maps),
+                            device=dev, batch_size=args.batch,
+                            epochs=args.epochs)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRTrainer
 
@@ -516,6 +531,18 @@ def cmd_predict(args) -> int:
                                               args.cross_layers),
                        cross_rank=hyper.get("cross_rank", args.cross_rank),
                        **kw), device=dev)
+    elif args.model == "xdeepfm":
+        from .models.xdeepfm import XDeepFMHyper, XDeepFMModel
+
+        # W^l is [cin_maps, H_{l-1}, nf]: the checkpoint's depth and maps
+        # where it has them
+        ckpt, kw = _concat_setup(args, ds, dev)
+        hyper = (ckpt or {}).get("hyper", {})
+        model = XDeepFMModel(
+            XDeepFMHyper(num_features=F, k=args.k, optimizer=args.optimizer,
+                         cin_layers=hyper.get("cin_layers", args.cin_layers),
+                         cin_maps=hyper.get("cin_maps", args.cin_maps),
+                         **kw), device=dev)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRModel
 
@@ -615,6 +642,13 @@ def build_parser():
                             "(predict: the checkpoint's)")
         p.add_argument("--cross-rank", type=int, default=64,
                        help="dcn2: rank of a cross layer's matrix, a "
+                            "multiple of 16 in 16..128 (predict: the "
+                            "checkpoint's)")
+        p.add_argument("--cin-layers", type=int, default=2,
+                       help="xdeepfm: number of CIN layers, 1..4 (predict: "
+                            "the checkpoint's)")
+        p.add_argument("--cin-maps", type=int, default=64,
+                       help="xdeepfm: feature maps of a CIN layer, a "
                             "multiple of 16 in 16..128 (predict: the "
                             "checkpoint's)")
         p.add_argument("--device", default=None)

@@ -6,6 +6,7 @@ from .wide_deep import WideDeepModel, WideDeepTrainer, WideDeepHyper
 from .deepfm import DeepFMModel, DeepFMTrainer, DeepFMHyper
 from .dcn import DCNModel, DCNTrainer, DCNHyper
 from .dcn2 import DCNv2Model, DCNv2Trainer, DCNv2Hyper
+from .xdeepfm import XDeepFMModel, XDeepFMTrainer, XDeepFMHyper
 from .mlp import MLP, DenseLayer
 from .gbm import GBMModel, GBMHyper
 from .gmm import GMMModel, GMMHyper
@@ -26,6 +27,7 @@ __all__ = [
     "DeepFMModel", "DeepFMTrainer", "DeepFMHyper",
     "DCNModel", "DCNTrainer", "DCNHyper",
     "DCNv2Model", "DCNv2Trainer", "DCNv2Hyper",
+    "XDeepFMModel", "XDeepFMTrainer", "XDeepFMHyper",
     "MLP", "DenseLayer",
     "GBMModel", "GBMHyper",
     "GMMModel", "GMMHyper",

@@ -2211,6 +2211,133 @@ std::vector<at::Tensor> dcn2_cross_backward(at::Tensor x0, at::Tensor X,
   return {G, S, dbc, du};
 }
 
+// ---- xDeepFM: the Compressed Interaction Network on the concat row ----
+
+struct CinDims {
+  int nf, K, H, L, B;
+};
+
+// Shared argument checks of the CIN bindings: x0 bf16 [B, nf*K], u [L, H];
+// the served range.
+CinDims check_cin_args(const at::Tensor& x0, const at::Tensor& u, int64_t nf,
+                       const char* op) {
+  check_cuda_f32(u, "u");
+  CHK(u.dim() == 2 && u.is_contiguous(), op, ": u must be [L, H]");
+  const int64_t L = u.size(0), H = u.size(1);
+  CHK(nf >= 1 && nf <= 64, op, ": nf must be in [1, 64], got ", nf);
+  CHK(H >= 16 && H % 16 == 0 && H <= 128, op,
+      ": the maps H must be a multiple of 16 in [16, 128], got ", H);
+  CHK(L >= 1 && L <= 4, op, ": 1 <= cin layers <= 4, got ", L);
+  CHK(x0.is_cuda(), "x0 must be on GPU");
+  CHK(x0.scalar_type() == at::kBFloat16, op, ": x0 must be bf16");
+  CHK(x0.is_contiguous(), "x0 must be contiguous");
+  CHK(x0.dim() == 2 && x0.size(1) >= nf && x0.size(1) % nf == 0, op,
+      ": x0 must be [B, nf*K] with nf = ", nf, ", got width ",
+      x0.dim() == 2 ? x0.size(1) : -1);
+  const int64_t d = x0.size(1), K = d / nf, B = x0.size(0);
+  CHK(d <= 1024, op, ": nf*K must be at most 1024, got ", d);
+  CHK(B * K < (1 << 24), op, ": B*K must be below 2^24, got ", B * K);
+  const long need = lightctr::cin_lds_bytes((int)nf, (int)H);
+  const long have = lightctr::ffm_max_lds_per_block();
+  CHK(need <= have, op, ": nf=", nf, ", H=", H, " needs ", need,
+      " bytes of LDS per block, the device gives ", have);
+  return {(int)nf, (int)K, (int)H, (int)L, (int)B};
+}
+
+// a flat bf16 mirror of the CIN weights in kernel order
+void check_cin_weights(const at::Tensor& t, const CinDims& s, const char* op,
+                       const char* name) {
+  CHK(t.is_cuda() && t.is_contiguous(), name,
+      " must be a contiguous GPU tensor");
+  CHK(t.scalar_type() == at::kBFloat16, op, ": ", name, " must be bf16");
+  const int64_t n = lightctr::cin_weight_elems(s.nf, s.H, s.L);
+  CHK(t.numel() == n, op, ": ", name, " must hold ", n, " elements, got ",
+      t.numel());
+  CHK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+      " must be 16-byte aligned");
+}
+
+void check_cin_saved(const at::Tensor& t, const CinDims& s, const char* op,
+                     const char* name) {
+  CHK(t.is_cuda() && t.is_contiguous(), name,
+      " must be a contiguous GPU tensor");
+  CHK(t.scalar_type() == at::kBFloat16, op, ": ", name, " must be bf16");
+  CHK(t.dim() == 4 && t.size(0) == s.L && t.size(1) == s.B &&
+          t.size(2) == s.K && t.size(3) == s.H,
+      op, ": ", name, " must be [", s.L, ", ", s.B, ", ", s.K, ", ", s.H, "]");
+  CHK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+      " must be 16-byte aligned");
+}
+
+// cin [B]; with save also X [L, B, K, H] (X^1 .. X^L, bf16)
+std::vector<at::Tensor> cin_forward(at::Tensor x0, at::Tensor Wbf,
+                                    at::Tensor u, int64_t nf, bool save) {
+  const char* op = "cin_forward";
+  const CinDims s = check_cin_args(x0, u, nf, op);
+  check_cin_weights(Wbf, s, op, "Wbf");
+  auto cin = at::empty({s.B}, u.options());
+  at::Tensor X;
+  if (save) X = at::empty({s.L, s.B, s.K, s.H}, x0.options());
+  if (s.B > 0) {
+    auto crow = at::empty({(int64_t)s.B * s.K}, u.options());
+    lightctr::cin_forward_launch(
+        x0.data_ptr(), Wbf.data_ptr(), u.data_ptr<float>(),
+        crow.data_ptr<float>(), cin.data_ptr<float>(),
+        save ? X.data_ptr() : nullptr, save, s.nf, s.K, s.H, s.L, s.B,
+        cur_stream());
+    C10_CUDA_KERNEL_LAUNCH_CHECK();
+  }
+  if (save) return {cin, X};
+  return {cin};
+}
+
+// (dX [L, B, K, H] bf16, du [L, H]); dDeep [B, nf*K] += dx0
+std::vector<at::Tensor> cin_backward(at::Tensor x0, at::Tensor X,
+                                     at::Tensor Wtbf, at::Tensor u,
+                                     at::Tensor dpred, at::Tensor dDeep,
+                                     int64_t nf) {
+  const char* op = "cin_backward";
+  const CinDims s = check_cin_args(x0, u, nf, op);
+  check_cin_weights(Wtbf, s, op, "Wtbf");
+  check_cin_saved(X, s, op, "X");
+  check_f32_n(dpred, s.B, "dpred");
+  check_f32_n(dDeep, (int64_t)s.B * s.nf * s.K, "dDeep");
+  CHK(dDeep.dim() == 2 && dDeep.size(1) == s.nf * s.K, op,
+      ": dDeep must be [B, ", s.nf * s.K, "]");
+  auto dX = at::empty({s.L, s.B, s.K, s.H}, x0.options());
+  auto du = at::empty({s.L, s.H}, u.options());
+  auto part = at::empty(
+      {lightctr::cin_du_chunks((long)s.B * s.K), s.L, s.H}, u.options());
+  lightctr::cin_backward_launch(
+      x0.data_ptr(), X.data_ptr(), Wtbf.data_ptr(), u.data_ptr<float>(),
+      dpred.data_ptr<float>(), dDeep.data_ptr<float>(), dX.data_ptr(),
+      part.data_ptr<float>(), du.data_ptr<float>(), s.nf, s.K, s.H, s.L, s.B,
+      cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {dX, du};
+}
+
+// dW: the flat fp32 gradient of the L weight matrices in kernel order
+at::Tensor cin_wgrad(at::Tensor x0, at::Tensor X, at::Tensor dX, at::Tensor u,
+                     int64_t nf) {
+  const char* op = "cin_wgrad";
+  const CinDims s = check_cin_args(x0, u, nf, op);
+  check_cin_saved(X, s, op, "X");
+  check_cin_saved(dX, s, op, "dX");
+  auto dW = at::empty({lightctr::cin_weight_elems(s.nf, s.H, s.L)},
+                      u.options());
+  int64_t cols = 0;
+  for (int l = 1; l <= s.L; ++l)
+    cols = std::max<int64_t>(cols, lightctr::cin_layer_cols(s.nf, s.H, l));
+  auto part = at::empty(
+      {lightctr::cin_wgrad_chunks((long)s.B * s.K), s.H, cols}, u.options());
+  lightctr::cin_wgrad_launch(x0.data_ptr(), X.data_ptr(), dX.data_ptr(),
+                             part.data_ptr<float>(), dW.data_ptr<float>(),
+                             s.nf, s.K, s.H, s.L, s.B, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return dW;
+}
+
 // ---- native data loader ----
 // Fast single-pass libffm parser ("label field:fid:val" per line) —
 // native equivalent of the reference's C++ loader
@@ -2832,6 +2959,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("d"), py::arg("r"));
   m.def("dcn2_cross_tile_rows", &lightctr::dcn2_cross_tile_rows,
         "rows per block tile of the DCN-v2 cross kernels");
+  m.def("cin_forward", &cin_forward,
+        "xDeepFM CIN on the bf16 concat, all layers in one launch: (cin [B]) "
+        "or, with save, (cin, X [L, B, K, H])",
+        py::arg("x0"), py::arg("Wbf"), py::arg("u"), py::arg("nf"),
+        py::arg("save"));
+  m.def("cin_backward", &cin_backward,
+        "CIN data backward, dDeep += dx0 in place: (dX [L, B, K, H], du)",
+        py::arg("x0"), py::arg("X"), py::arg("Wtbf"), py::arg("u"),
+        py::arg("dpred"), py::arg("dDeep"), py::arg("nf"));
+  m.def("cin_wgrad", &cin_wgrad,
+        "CIN weight gradient, flat in kernel order", py::arg("x0"),
+        py::arg("X"), py::arg("dX"), py::arg("u"), py::arg("nf"));
+  m.def("cin_tile_rows", &lightctr::cin_tile_rows,
+        "(b, d) rows per block tile of the CIN kernels");
+  m.def("cin_layer_cols", &lightctr::cin_layer_cols,
+        "columns of layer l's weight matrix in kernel order", py::arg("nf"),
+        py::arg("H"), py::arg("l"));
+  m.def("cin_lds_bytes", &lightctr::cin_lds_bytes,
+        "dynamic LDS per block the CIN kernels need", py::arg("nf"),
+        py::arg("H"));
   m.def("wide_forward", &wide_forward, "LR wide forward sum");
   m.def("w2v_negsample_step", &w2v_negsample_step,
         "fused CBOW negative-sampling train step (Hogwild)");

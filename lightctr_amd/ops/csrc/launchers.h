@@ -390,6 +390,27 @@ void dcn2_cross_backward_launch(const void* x0, const void* X, const void* T,
                                 float* dbc, float* du, int L, int d, int r,
                                 int B, ihipStream_t* stream);
 
+// --- cin_kernels.hip (xDeepFM's CIN; x0: bf16 [B, nf*K]; Wbf / Wtbf: the
+// flat bf16 mirrors of the L weight matrices in kernel order, [H, Kl] and
+// [Kl, H] a layer; X, dX: bf16 [L, B*K, H]; 1 <= nf <= 64, nf*K <= 1024,
+// H % 16 == 0, 16 <= H <= 128, 1 <= L <= 4, B*K < 2^24) ---
+int cin_tile_rows();
+long cin_layer_cols(int nf, int H, int l);
+long cin_weight_elems(int nf, int H, int L);
+long cin_lds_bytes(int nf, int H);
+int cin_wgrad_chunks(long BK);
+int cin_du_chunks(long BK);
+void cin_forward_launch(const void* x0, const void* Wbf, const float* u,
+                        float* crow, float* cin, void* X, bool save, int nf,
+                        int K, int H, int L, int B, ihipStream_t* stream);
+void cin_backward_launch(const void* x0, const void* X, const void* Wtbf,
+                         const float* u, const float* dpred, float* dDeep,
+                         void* dX, float* part, float* du, int nf, int K,
+                         int H, int L, int B, ihipStream_t* stream);
+void cin_wgrad_launch(const void* x0, const void* X, const void* dX,
+                      float* part, float* dW, int nf, int K, int H, int L,
+                      int B, ihipStream_t* stream);
+
 // --- codec_kernels.hip ---
 void quantile_encode_launch(const float* x, unsigned char* code,
                             const float* table, int levels, long n,
