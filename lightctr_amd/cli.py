@@ -15,6 +15,8 @@ command:
         --cross-rank 64 ...       (DCN-v2, low-rank matrix cross layers)
     python -m lightctr_amd.cli train|predict --model xdeepfm --cin-layers 2 \\
         --cin-maps 64 ...         (xDeepFM, compressed interaction network)
+    python -m lightctr_amd.cli train|predict --model autoint --attn-layers 3 \\
+        --attn-heads 2 --attn-dim 32 ...  (AutoInt, field self-attention)
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
     python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
         --data dense.csv ...      (dense rows; served by the compiled forest)
@@ -57,7 +59,7 @@ def _load_data(args):
 def cmd_train(args) -> int:
     dev = _device(args)
     if args.model not in ("fm", "ffm", "fwfm", "nfm", "widedeep", "deepfm",
-                          "dcn", "dcn2", "xdeepfm", "lr"):
+                          "dcn", "dcn2", "xdeepfm", "autoint", "lr"):
         # the rest of the zoo reads dense / text data, not libffm
         return _train_other(args, dev)
     ds = _load_data(args)
@@ -150,6 +152,20 @@ def cmd_train(args) -> int:
                                              pooling=args.pooling,
                                              cin_layers=args.cin_layers,
                                              cin_maps=args.cin_maps),
+                            device=dev, batch_size=args.batch,
+                            epochs=args.epochs)
+    elif args.model == "autoint":
+        from .models.autoint import AutoIntHyper, AutoIntTrainer
+
+        tr = AutoIntTrainer(ds, AutoIntHyper(num_features=F,
+                                             num_fields=ds.num_fields,
+                                             k=args.k,
+                                             optimizer=args.optimizer,
+                                             lr=args.lr, layout=args.layout,
+                                             pooling=args.pooling,
+                                             attn_layers=args.attn_layers,
+                                             attn_heads=args.attn_heads,
+                                             attn_dim=args.attn_dim),
                             device=dev, batch_size=args.batch,
                             epochs=args.epochs)
     elif args.model == "lr":
@@ -543,6 +559,18 @@ def cmd_predict(args) -> int:
                          cin_layers=hyper.get("cin_layers", args.cin_layers),
                          cin_maps=hyper.get("cin_maps", args.cin_maps),
                          **kw), device=dev)
+    elif args.model == "autoint":
+        from .models.autoint import AutoIntHyper, AutoIntModel
+
+        # W^l is [d_in, 4 heads dim]: the checkpoint's depth, heads and
+        # head width where it has them
+        ckpt, kw = _concat_setup(args, ds, dev)
+        hyper = (ckpt or {}).get("hyper", {})
+        model = AutoIntModel(
+            AutoIntHyper(num_features=F, k=args.k, optimizer=args.optimizer,
+                         **{n: hyper.get(n, getattr(args, n)) for n in
+                            ("attn_layers", "attn_heads", "attn_dim")},
+                         **kw), device=dev)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRModel
 
@@ -651,6 +679,15 @@ def build_parser():
                        help="xdeepfm: feature maps of a CIN layer, a "
                             "multiple of 16 in 16..128 (predict: the "
                             "checkpoint's)")
+        p.add_argument("--attn-layers", type=int, default=3,
+                       help="autoint: number of attention layers, 1..4 "
+                            "(predict: the checkpoint's)")
+        p.add_argument("--attn-heads", type=int, default=2,
+                       help="autoint: heads of a layer, 1, 2 or 4 (predict: "
+                            "the checkpoint's)")
+        p.add_argument("--attn-dim", type=int, default=32,
+                       help="autoint: width of a head, 16 or 32, "
+                            "heads*dim <= 64 (predict: the checkpoint's)")
         p.add_argument("--device", default=None)
         p.add_argument("--seed", type=int, default=1234)
         p.add_argument("--save", default=None)

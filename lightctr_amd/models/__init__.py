@@ -7,6 +7,7 @@ from .deepfm import DeepFMModel, DeepFMTrainer, DeepFMHyper
 from .dcn import DCNModel, DCNTrainer, DCNHyper
 from .dcn2 import DCNv2Model, DCNv2Trainer, DCNv2Hyper
 from .xdeepfm import XDeepFMModel, XDeepFMTrainer, XDeepFMHyper
+from .autoint import AutoIntModel, AutoIntTrainer, AutoIntHyper
 from .mlp import MLP, DenseLayer
 from .gbm import GBMModel, GBMHyper
 from .gmm import GMMModel, GMMHyper
@@ -28,6 +29,7 @@ __all__ = [
     "DCNModel", "DCNTrainer", "DCNHyper",
     "DCNv2Model", "DCNv2Trainer", "DCNv2Hyper",
     "XDeepFMModel", "XDeepFMTrainer", "XDeepFMHyper",
+    "AutoIntModel", "AutoIntTrainer", "AutoIntHyper",
     "MLP", "DenseLayer",
     "GBMModel", "GBMHyper",
     "GMMModel", "GMMHyper",

@@ -2338,6 +2338,110 @@ at::Tensor cin_wgrad(at::Tensor x0, at::Tensor X, at::Tensor dX, at::Tensor u,
   return dW;
 }
 
+// ---- AutoInt: multi-head self-attention over the fields of the concat ----
+
+struct AutoIntDims {
+  int nf, K, heads, hd, D, L, B;
+};
+
+// Shared argument checks of the AutoInt bindings: x0 bf16 [B, nf*K], Wbf the
+// flat bf16 mirror of W^1 [K, 4D], W^l [D, 4D], u [nf, D]; the served range.
+AutoIntDims check_autoint_args(const at::Tensor& x0, const at::Tensor& Wbf,
+                               const at::Tensor& u, int64_t nf, int64_t heads,
+                               int64_t hd, const char* op) {
+  CHK(nf >= 1 && nf <= 64, op, ": nf must be in [1, 64], got ", nf);
+  CHK(heads == 1 || heads == 2 || heads == 4, op,
+      ": heads must be 1, 2 or 4, got ", heads);
+  CHK(hd == 16 || hd == 32, op, ": head_dim must be 16 or 32, got ", hd);
+  const int64_t D = heads * hd;
+  CHK(D <= 64, op, ": heads*head_dim must be at most 64, got ", D);
+  CHK(x0.is_cuda(), "x0 must be on GPU");
+  CHK(x0.scalar_type() == at::kBFloat16, op, ": x0 must be bf16");
+  CHK(x0.is_contiguous(), "x0 must be contiguous");
+  CHK(x0.dim() == 2 && x0.size(1) >= nf && x0.size(1) % nf == 0, op,
+      ": x0 must be [B, nf*K] with nf = ", nf, ", got width ",
+      x0.dim() == 2 ? x0.size(1) : -1);
+  const int64_t d = x0.size(1), K = d / nf, B = x0.size(0);
+  CHK(d <= 1024, op, ": nf*K must be at most 1024, got ", d);
+  CHK(K <= 64, op, ": K must be at most 64, got ", K);
+  CHK(Wbf.is_cuda() && Wbf.is_contiguous(),
+      "Wbf must be a contiguous GPU tensor");
+  CHK(Wbf.scalar_type() == at::kBFloat16, op, ": Wbf must be bf16");
+  const int64_t rows = Wbf.numel() / (4 * D) - K;
+  CHK(Wbf.numel() % (4 * D) == 0 && rows >= 0 && rows % D == 0, op,
+      ": Wbf must hold (K + (L-1) D) * 4D elements, got ", Wbf.numel());
+  const int64_t L = rows / D + 1;
+  CHK(L >= 1 && L <= 4, op, ": 1 <= attention layers <= 4, got ", L);
+  CHK((uintptr_t)Wbf.data_ptr() % 16 == 0 && (uintptr_t)x0.data_ptr() % 16 == 0,
+      op, ": x0 and Wbf must be 16-byte aligned");
+  check_f32_n(u, nf * D, "u");
+  CHK(B * nf < (1 << 24), op, ": B*nf must be below 2^24, got ", B * nf);
+  const long need =
+      lightctr::autoint_lds_bytes((int)nf, (int)K, (int)heads, (int)hd, (int)L);
+  const long have = std::min<long>(lightctr::ffm_max_lds_per_block(), 160 * 1024);
+  CHK(need <= have, op, ": nf=", nf, ", K=", K, ", D=", D, ", L=", L,
+      " needs ", need, " bytes of LDS per block, the device gives ", have);
+  return {(int)nf, (int)K, (int)heads, (int)hd, (int)D, (int)L, (int)B};
+}
+
+// ai [B]; with save also X [L, B, nf, D] (X^1 .. X^L, bf16)
+std::vector<at::Tensor> autoint_forward(at::Tensor x0, at::Tensor Wbf,
+                                        at::Tensor u, int64_t nf,
+                                        int64_t heads, int64_t head_dim,
+                                        bool save) {
+  const char* op = "autoint_forward";
+  const AutoIntDims s = check_autoint_args(x0, Wbf, u, nf, heads, head_dim, op);
+  auto ai = at::empty({s.B}, u.options());
+  at::Tensor X;
+  if (save) X = at::empty({s.L, s.B, s.nf, s.D}, x0.options());
+  if (s.B > 0) {
+    lightctr::autoint_forward_launch(
+        x0.data_ptr(), Wbf.data_ptr(), u.data_ptr<float>(),
+        ai.data_ptr<float>(), save ? X.data_ptr() : nullptr, save, s.nf, s.K,
+        s.heads, s.hd, s.L, s.B, cur_stream());
+    C10_CUDA_KERNEL_LAUNCH_CHECK();
+  }
+  if (save) return {ai, X};
+  return {ai};
+}
+
+// (dW flat fp32 in the layout of W, du [nf, D]); dDeep [B, nf*K] += dx0
+std::vector<at::Tensor> autoint_backward(at::Tensor x0, at::Tensor X,
+                                         at::Tensor Wbf, at::Tensor Wtbf,
+                                         at::Tensor u, at::Tensor dpred,
+                                         at::Tensor dDeep, int64_t nf,
+                                         int64_t heads, int64_t head_dim) {
+  const char* op = "autoint_backward";
+  const AutoIntDims s = check_autoint_args(x0, Wbf, u, nf, heads, head_dim, op);
+  CHK(Wtbf.is_cuda() && Wtbf.scalar_type() == at::kBFloat16 &&
+          Wtbf.numel() == Wbf.numel(),
+      op, ": Wtbf must be the bf16 transposed mirror of Wbf");
+  CHK(X.is_cuda() && X.is_contiguous() && X.scalar_type() == at::kBFloat16,
+      op, ": X must be a contiguous bf16 GPU tensor");
+  CHK(X.dim() == 4 && X.size(0) == s.L && X.size(1) == s.B &&
+          X.size(2) == s.nf && X.size(3) == s.D,
+      op, ": X must be [", s.L, ", ", s.B, ", ", s.nf, ", ", s.D, "]");
+  check_f32_n(dpred, s.B, "dpred");
+  check_f32_n(dDeep, (int64_t)s.B * s.nf * s.K, "dDeep");
+  CHK(dDeep.dim() == 2 && dDeep.size(1) == s.nf * s.K, op,
+      ": dDeep must be [B, ", s.nf * s.K, "]");
+  const int64_t T = (int64_t)s.B * s.nf;
+  auto dW = at::empty({Wbf.numel()}, u.options());
+  auto du = at::empty({s.nf, s.D}, u.options());
+  auto G = at::empty({s.L, T, 4 * s.D}, x0.options());
+  const int64_t pw = (int64_t)lightctr::autoint_wgrad_chunks(T) *
+                     std::max(s.K, s.D) * 4 * s.D;
+  const int64_t pu = (int64_t)lightctr::autoint_du_chunks(s.B) * s.nf * s.D;
+  auto part = at::empty({std::max<int64_t>(std::max(pw, pu), 1)}, u.options());
+  lightctr::autoint_backward_launch(
+      x0.data_ptr(), X.data_ptr(), Wbf.data_ptr(), u.data_ptr<float>(),
+      dpred.data_ptr<float>(), dDeep.data_ptr<float>(), G.data_ptr(),
+      part.data_ptr<float>(), dW.data_ptr<float>(), du.data_ptr<float>(),
+      s.nf, s.K, s.heads, s.hd, s.L, s.B, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  return {dW, du};
+}
+
 // ---- native data loader ----
 // Fast single-pass libffm parser ("label field:fid:val" per line) —
 // native equivalent of the reference's C++ loader
@@ -2979,6 +3083,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cin_lds_bytes", &lightctr::cin_lds_bytes,
         "dynamic LDS per block the CIN kernels need", py::arg("nf"),
         py::arg("H"));
+  m.def("autoint_forward", &autoint_forward,
+        "AutoInt attention layers on the bf16 concat, all layers in one "
+        "launch: (ai [B]) or, with save, (ai, X [L, B, nf, D])",
+        py::arg("x0"), py::arg("Wbf"), py::arg("u"), py::arg("nf"),
+        py::arg("heads"), py::arg("head_dim"), py::arg("save"));
+  m.def("autoint_backward", &autoint_backward,
+        "AutoInt backward, dDeep += dx0 in place: (dW flat, du [nf, D])",
+        py::arg("x0"), py::arg("X"), py::arg("Wbf"), py::arg("Wtbf"),
+        py::arg("u"), py::arg("dpred"), py::arg("dDeep"), py::arg("nf"),
+        py::arg("heads"), py::arg("head_dim"));
+  m.def("autoint_tile_rows", &lightctr::autoint_tile_rows,
+        "examples per block tile of the AutoInt kernels");
+  m.def("autoint_lds_bytes", &lightctr::autoint_lds_bytes,
+        "dynamic LDS per block the AutoInt kernels need at the least",
+        py::arg("nf"), py::arg("K"), py::arg("heads"), py::arg("head_dim"),
+        py::arg("L"));
   m.def("wide_forward", &wide_forward, "LR wide forward sum");
   m.def("w2v_negsample_step", &w2v_negsample_step,
         "fused CBOW negative-sampling train step (Hogwild)");

@@ -411,6 +411,24 @@ void cin_wgrad_launch(const void* x0, const void* X, const void* dX,
                       float* part, float* dW, int nf, int K, int H, int L,
                       int B, ihipStream_t* stream);
 
+// --- autoint_kernels.hip (AutoInt's attention layers; x0: bf16 [B, nf*K];
+// Wbf: the flat bf16 mirror of the L matrices W^l [d_in, 4D], D = heads*hd;
+// X: bf16 [L, B, nf, D]; G: bf16 [L, B*nf, 4D]; 1 <= nf <= 64, K <= 64,
+// heads in {1, 2, 4}, hd in {16, 32}, D <= 64, 1 <= L <= 4, B*nf < 2^24) ---
+int autoint_tile_rows();
+long autoint_lds_bytes(int nf, int K, int heads, int hd, int L);
+int autoint_wgrad_chunks(long T);
+int autoint_du_chunks(int B);
+void autoint_forward_launch(const void* x0, const void* Wbf, const float* u,
+                            float* ai, void* X, bool save, int nf, int K,
+                            int heads, int hd, int L, int B,
+                            ihipStream_t* stream);
+void autoint_backward_launch(const void* x0, const void* X, const void* Wbf,
+                             const float* u, const float* dpred,
+                             float* dDeep, void* G, float* part, float* dW,
+                             float* du, int nf, int K, int heads, int hd,
+                             int L, int B, ihipStream_t* stream);
+
 // --- codec_kernels.hip ---
 void quantile_encode_launch(const float* x, unsigned char* code,
                             const float* table, int levels, long n,
