@@ -17,6 +17,8 @@ command:
         --cin-maps 64 ...         (xDeepFM, compressed interaction network)
     python -m lightctr_amd.cli train|predict --model autoint --attn-layers 3 \\
         --attn-heads 2 --attn-dim 32 ...  (AutoInt, field self-attention)
+    python -m lightctr_amd.cli train|predict --model afm --attn-factor 32 \\
+        ...                       (AFM, attention over the pair products)
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
     python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
         --data dense.csv ...      (dense rows; served by the compiled forest)
@@ -59,7 +61,8 @@ def _load_data(args):
 def cmd_train(args) -> int:
     dev = _device(args)
     if args.model not in ("fm", "ffm", "fwfm", "nfm", "widedeep", "deepfm",
-                          "dcn", "dcn2", "xdeepfm", "autoint", "lr"):
+                          "dcn", "dcn2", "xdeepfm", "autoint", "afm",
+                          "lr"):
         # the rest of the zoo reads dense / text data, not libffm
         return _train_other(args, dev)
     ds = _load_data(args)
@@ -168,6 +171,17 @@ def cmd_train(args) -> int:
                                              attn_dim=args.attn_dim),
                             device=dev, batch_size=args.batch,
                             epochs=args.epochs)
+    elif args.model == "afm":
+        from .models.afm import AFMHyper, AFMTrainer
+
+        tr = AFMTrainer(ds, AFMHyper(num_features=F,
+                                     num_fields=ds.num_fields, k=args.k,
+                                     optimizer=args.optimizer, lr=args.lr,
+                                     layout=args.layout,
+                                     pooling=args.pooling,
+                                     attn_factor=args.attn_factor),
+                        device=dev, batch_size=args.batch,
+                        epochs=args.epochs)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRTrainer
 
@@ -571,6 +585,16 @@ def cmd_predict(args) -> int:
                          **{n: hyper.get(n, getattr(args, n)) for n in
                             ("attn_layers", "attn_heads", "attn_dim")},
                          **kw), device=dev)
+    elif args.model == "afm":
+        from .models.afm import AFMHyper, AFMModel
+
+        # Wa is [k, attn_factor]: the checkpoint's width where it has one
+        ckpt, kw = _concat_setup(args, ds, dev)
+        hyper = (ckpt or {}).get("hyper", {})
+        model = AFMModel(
+            AFMHyper(num_features=F, k=args.k, optimizer=args.optimizer,
+                     attn_factor=hyper.get("attn_factor", args.attn_factor),
+                     **kw), device=dev)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRModel
 
@@ -688,6 +712,9 @@ def build_parser():
         p.add_argument("--attn-dim", type=int, default=32,
                        help="autoint: width of a head, 16 or 32, "
                             "heads*dim <= 64 (predict: the checkpoint's)")
+        p.add_argument("--attn-factor", type=int, default=32,
+                       help="afm: width of the attention net, a multiple of "
+                            "16 in 16..64 (predict: the checkpoint's)")
         p.add_argument("--device", default=None)
         p.add_argument("--seed", type=int, default=1234)
         p.add_argument("--save", default=None)

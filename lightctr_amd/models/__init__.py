@@ -8,6 +8,7 @@ from .dcn import DCNModel, DCNTrainer, DCNHyper
 from .dcn2 import DCNv2Model, DCNv2Trainer, DCNv2Hyper
 from .xdeepfm import XDeepFMModel, XDeepFMTrainer, XDeepFMHyper
 from .autoint import AutoIntModel, AutoIntTrainer, AutoIntHyper
+from .afm import AFMModel, AFMTrainer, AFMHyper
 from .mlp import MLP, DenseLayer
 from .gbm import GBMModel, GBMHyper
 from .gmm import GMMModel, GMMHyper
@@ -30,6 +31,7 @@ __all__ = [
     "DCNv2Model", "DCNv2Trainer", "DCNv2Hyper",
     "XDeepFMModel", "XDeepFMTrainer", "XDeepFMHyper",
     "AutoIntModel", "AutoIntTrainer", "AutoIntHyper",
+    "AFMModel", "AFMTrainer", "AFMHyper",
     "MLP", "DenseLayer",
     "GBMModel", "GBMHyper",
     "GMMModel", "GMMHyper",

@@ -2442,6 +2442,101 @@ std::vector<at::Tensor> autoint_backward(at::Tensor x0, at::Tensor X,
   return {dW, du};
 }
 
+// ---- AFM: attention over the pairwise products of the concat's fields ----
+
+struct AfmDims {
+  int nf, K, A, B;
+};
+
+// Shared argument checks of the AFM bindings: x0 bf16 [B, nf*K], Wbf the bf16
+// mirror of Wa [K, A], ba and qa [A], ua [K]; the served range.
+AfmDims check_afm_args(const at::Tensor& x0, const at::Tensor& Wbf,
+                       const at::Tensor& ba, const at::Tensor& qa,
+                       const at::Tensor& ua, int64_t nf, const char* op) {
+  CHK(nf >= 2 && nf <= 64, op, ": nf must be in [2, 64], got ", nf);
+  CHK(x0.is_cuda(), "x0 must be on GPU");
+  CHK(x0.scalar_type() == at::kBFloat16, op, ": x0 must be bf16");
+  CHK(x0.is_contiguous(), "x0 must be contiguous");
+  CHK(x0.dim() == 2 && x0.size(1) >= nf && x0.size(1) % nf == 0, op,
+      ": x0 must be [B, nf*K] with nf = ", nf, ", got width ",
+      x0.dim() == 2 ? x0.size(1) : -1);
+  const int64_t d = x0.size(1), K = d / nf, B = x0.size(0);
+  CHK(d <= 1024, op, ": nf*K must be at most 1024, got ", d);
+  CHK(K <= 64, op, ": K must be at most 64, got ", K);
+  check_cuda_f32(ba, "ba");
+  const int64_t A = ba.numel();
+  CHK(A % 16 == 0 && A >= 16 && A <= 64, op,
+      ": A must be a multiple of 16 in [16, 64], got ", A);
+  check_f32_n(qa, A, "qa");
+  check_f32_n(ua, K, "ua");
+  CHK(Wbf.is_cuda() && Wbf.is_contiguous(),
+      "Wbf must be a contiguous GPU tensor");
+  CHK(Wbf.scalar_type() == at::kBFloat16, op, ": Wbf must be bf16");
+  CHK(Wbf.numel() == K * A, op, ": Wbf must hold K*A = ", K * A,
+      " elements, got ", Wbf.numel());
+  CHK(B * nf < (1 << 24), op, ": B*nf must be below 2^24, got ", B * nf);
+  const long need = lightctr::afm_lds_bytes((int)nf, (int)K, (int)A);
+  const long have = std::min<long>(lightctr::ffm_max_lds_per_block(), 160 * 1024);
+  CHK(need <= have, op, ": nf=", nf, ", K=", K, ", A=", A, " needs ", need,
+      " bytes of LDS per block, the device gives ", have);
+  return {(int)nf, (int)K, (int)A, (int)B};
+}
+
+// (afm [B], lse [B]); lse (the log-sum-exp of the pair scores, what the
+// backward reads) is empty without save
+std::vector<at::Tensor> afm_forward(at::Tensor x0, at::Tensor Wbf,
+                                    at::Tensor ba, at::Tensor qa,
+                                    at::Tensor ua, int64_t nf, bool save) {
+  const char* op = "afm_forward";
+  const AfmDims s = check_afm_args(x0, Wbf, ba, qa, ua, nf, op);
+  auto afm = at::empty({s.B}, ua.options());
+  auto lse = at::empty({save ? s.B : 0}, ua.options());
+  if (s.B > 0) {
+    lightctr::afm_forward_launch(
+        x0.data_ptr(), Wbf.data_ptr(), ba.data_ptr<float>(),
+        qa.data_ptr<float>(), ua.data_ptr<float>(), afm.data_ptr<float>(),
+        save ? lse.data_ptr<float>() : nullptr, save, s.nf, s.K, s.A, s.B,
+        cur_stream());
+    C10_CUDA_KERNEL_LAUNCH_CHECK();
+  }
+  return {afm, lse};
+}
+
+// (dWa [K, A], dba, dqa, dua); dDeep [B, nf*K] += dx0
+std::vector<at::Tensor> afm_backward(at::Tensor x0, at::Tensor lse,
+                                     at::Tensor afm, at::Tensor Wbf,
+                                     at::Tensor Wtbf, at::Tensor ba,
+                                     at::Tensor qa, at::Tensor ua,
+                                     at::Tensor dpred, at::Tensor dDeep,
+                                     int64_t nf) {
+  const char* op = "afm_backward";
+  const AfmDims s = check_afm_args(x0, Wbf, ba, qa, ua, nf, op);
+  CHK(Wtbf.is_cuda() && Wtbf.is_contiguous() &&
+          Wtbf.scalar_type() == at::kBFloat16 && Wtbf.numel() == Wbf.numel(),
+      op, ": Wtbf must be the bf16 transposed mirror of Wbf");
+  check_f32_n(lse, s.B, "lse");
+  check_f32_n(afm, s.B, "afm");
+  check_f32_n(dpred, s.B, "dpred");
+  check_f32_n(dDeep, (int64_t)s.B * s.nf * s.K, "dDeep");
+  CHK(dDeep.dim() == 2 && dDeep.size(1) == s.nf * s.K, op,
+      ": dDeep must be [B, ", s.nf * s.K, "]");
+  const int64_t n = (int64_t)s.K * s.A + 2 * s.A + s.K;
+  auto out = at::empty({n}, ua.options());
+  auto part = at::empty(
+      {std::max<int64_t>((int64_t)lightctr::afm_backward_chunks(s.B) * n, 1)},
+      ua.options());
+  lightctr::afm_backward_launch(
+      x0.data_ptr(), lse.data_ptr<float>(), afm.data_ptr<float>(),
+      Wbf.data_ptr(), Wtbf.data_ptr(), ba.data_ptr<float>(),
+      qa.data_ptr<float>(), ua.data_ptr<float>(), dpred.data_ptr<float>(),
+      dDeep.data_ptr<float>(), part.data_ptr<float>(), out.data_ptr<float>(),
+      s.nf, s.K, s.A, s.B, cur_stream());
+  C10_CUDA_KERNEL_LAUNCH_CHECK();
+  const int64_t ka = (int64_t)s.K * s.A;
+  return {out.narrow(0, 0, ka).view({s.K, s.A}), out.narrow(0, ka, s.A),
+          out.narrow(0, ka + s.A, s.A), out.narrow(0, ka + 2 * s.A, s.K)};
+}
+
 // ---- native data loader ----
 // Fast single-pass libffm parser ("label field:fid:val" per line) —
 // native equivalent of the reference's C++ loader
@@ -3099,6 +3194,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dynamic LDS per block the AutoInt kernels need at the least",
         py::arg("nf"), py::arg("K"), py::arg("heads"), py::arg("head_dim"),
         py::arg("L"));
+  m.def("afm_forward", &afm_forward,
+        "AFM pair attention on the bf16 concat: (afm [B], lse [B]), lse "
+        "empty without save",
+        py::arg("x0"), py::arg("Wabf"), py::arg("ba"), py::arg("qa"),
+        py::arg("ua"), py::arg("nf"), py::arg("save"));
+  m.def("afm_backward", &afm_backward,
+        "AFM backward, dDeep += dx0 in place: (dWa [K, A], dba, dqa, dua)",
+        py::arg("x0"), py::arg("lse"), py::arg("afm"), py::arg("Wabf"),
+        py::arg("Watbf"), py::arg("ba"), py::arg("qa"), py::arg("ua"),
+        py::arg("dpred"), py::arg("dDeep"), py::arg("nf"));
+  m.def("afm_tile_rows", &lightctr::afm_tile_rows,
+        "examples per block tile of the AFM kernels");
+  m.def("afm_lds_bytes", &lightctr::afm_lds_bytes,
+        "dynamic LDS per block the AFM kernels need", py::arg("nf"),
+        py::arg("K"), py::arg("A"));
+  m.def("afm_backward_chunks", &lightctr::afm_backward_chunks,
+        "partials of the AFM parameter gradients for a batch", py::arg("B"));
   m.def("wide_forward", &wide_forward, "LR wide forward sum");
   m.def("w2v_negsample_step", &w2v_negsample_step,
         "fused CBOW negative-sampling train step (Hogwild)");

@@ -429,6 +429,22 @@ void autoint_backward_launch(const void* x0, const void* X, const void* Wbf,
                              float* du, int nf, int K, int heads, int hd,
                              int L, int B, ihipStream_t* stream);
 
+// --- afm_kernels.hip (attentional FM; x0: bf16 [B, nf*K]; Wbf [K, A] and
+// Wtbf [A, K]: the bf16 mirrors of Wa; 2 <= nf <= 64, K <= 64,
+// nf*K <= 1024, A % 16 == 0, 16 <= A <= 64, B*nf < 2^24) ---
+int afm_tile_rows();
+long afm_lds_bytes(int nf, int K, int A);
+int afm_backward_chunks(int B);
+void afm_forward_launch(const void* x0, const void* Wbf, const float* ba,
+                        const float* qa, const float* ua, float* afm,
+                        float* lse, bool save, int nf, int K, int A, int B,
+                        ihipStream_t* stream);
+void afm_backward_launch(const void* x0, const float* lse, const float* afm,
+                         const void* Wbf, const void* Wtbf, const float* ba,
+                         const float* qa, const float* ua, const float* dpred,
+                         float* dDeep, float* part, float* out, int nf, int K,
+                         int A, int B, ihipStream_t* stream);
+
 // --- codec_kernels.hip ---
 void quantile_encode_launch(const float* x, unsigned char* code,
                             const float* table, int levels, long n,
