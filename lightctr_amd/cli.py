@@ -19,6 +19,8 @@ command:
         --attn-heads 2 --attn-dim 32 ...  (AutoInt, field self-attention)
     python -m lightctr_amd.cli train|predict --model afm --attn-factor 32 \\
         ...                       (AFM, attention over the pair products)
+    python -m lightctr_amd.cli train|predict --model pnn ...
+        (PNN, the pairs' inner products in front of the MLP)
     python -m lightctr_amd.cli predict --model fm --load m.pt --data t.csv
     python -m lightctr_amd.cli train|predict --model gbm|gbdt_lr \
         --data dense.csv ...      (dense rows; served by the compiled forest)
@@ -61,7 +63,7 @@ def _load_data(args):
 def cmd_train(args) -> int:
     dev = _device(args)
     if args.model not in ("fm", "ffm", "fwfm", "nfm", "widedeep", "deepfm",
-                          "dcn", "dcn2", "xdeepfm", "autoint", "afm",
+                          "dcn", "dcn2", "xdeepfm", "autoint", "afm", "pnn",
                           "lr"):
         # the rest of the zoo reads dense / text data, not libffm
         return _train_other(args, dev)
@@ -180,6 +182,16 @@ def cmd_train(args) -> int:
                                      layout=args.layout,
                                      pooling=args.pooling,
                                      attn_factor=args.attn_factor),
+                        device=dev, batch_size=args.batch,
+                        epochs=args.epochs)
+    elif args.model == "pnn":
+        from .models.pnn import PNNHyper, PNNTrainer
+
+        tr = PNNTrainer(ds, PNNHyper(num_features=F,
+                                     num_fields=ds.num_fields, k=args.k,
+                                     optimizer=args.optimizer, lr=args.lr,
+                                     layout=args.layout,
+                                     pooling=args.pooling),
                         device=dev, batch_size=args.batch,
                         epochs=args.epochs)
     elif args.model == "lr":
@@ -595,6 +607,13 @@ def cmd_predict(args) -> int:
             AFMHyper(num_features=F, k=args.k, optimizer=args.optimizer,
                      attn_factor=hyper.get("attn_factor", args.attn_factor),
                      **kw), device=dev)
+    elif args.model == "pnn":
+        from .models.pnn import PNNHyper, PNNModel
+
+        ckpt, kw = _concat_setup(args, ds, dev)
+        model = PNNModel(PNNHyper(num_features=F, k=args.k,
+                                  optimizer=args.optimizer, **kw),
+                         device=dev)
     elif args.model == "lr":
         from .models.lr import LRHyper, LRModel
 

@@ -9,6 +9,7 @@ from .dcn2 import DCNv2Model, DCNv2Trainer, DCNv2Hyper
 from .xdeepfm import XDeepFMModel, XDeepFMTrainer, XDeepFMHyper
 from .autoint import AutoIntModel, AutoIntTrainer, AutoIntHyper
 from .afm import AFMModel, AFMTrainer, AFMHyper
+from .pnn import PNNModel, PNNTrainer, PNNHyper
 from .mlp import MLP, DenseLayer
 from .gbm import GBMModel, GBMHyper
 from .gmm import GMMModel, GMMHyper
@@ -32,6 +33,7 @@ __all__ = [
     "XDeepFMModel", "XDeepFMTrainer", "XDeepFMHyper",
     "AutoIntModel", "AutoIntTrainer", "AutoIntHyper",
     "AFMModel", "AFMTrainer", "AFMHyper",
+    "PNNModel", "PNNTrainer", "PNNHyper",
     "MLP", "DenseLayer",
     "GBMModel", "GBMHyper",
     "GMMModel", "GMMHyper",

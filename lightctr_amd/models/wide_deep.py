@@ -75,7 +75,7 @@ class WideDeepModel(BagLayout):
         if hyper.optimizer == "ftrl":
             self.zW = torch.zeros_like(self.W)
             self.zE = torch.zeros_like(self.E)
-        dims = [nf * K, *hyper.hidden, 1]
+        dims = [self._mlp_in_dim(), *hyper.hidden, 1]
         self.mlp = MLP(dims, optimizer=hyper.mlp_optimizer, lr=hyper.mlp_lr,
                        dropout=hyper.dropout, seed=hyper.seed, device=device)
         nwords = (F + 63) // 64
@@ -87,6 +87,10 @@ class WideDeepModel(BagLayout):
         self._gpu = self.device.type == "cuda"
         if self._gpu:
             require_hip_ops()
+
+    def _mlp_in_dim(self):
+        """width of the MLP's input: the concat row (PNN widens it)"""
+        return self.h.num_fields * self.h.k
 
     def _gather_cpu(self, row_ptr, fids, vals):
         B = row_ptr.numel() - 1

@@ -2537,6 +2537,72 @@ std::vector<at::Tensor> afm_backward(at::Tensor x0, at::Tensor lse,
           out.narrow(0, ka + s.A, s.A), out.narrow(0, ka + 2 * s.A, s.K)};
 }
 
+// ---- PNN: the inner-product layer in front of the MLP ----
+
+// Shared argument checks of the PNN bindings: the served range of (nf, K) and
+// the batch; returns Dz.
+int64_t check_pnn_dims(int64_t nf, int64_t K, int64_t B, const char* op) {
+  CHK(nf >= 2 && nf <= 64, op, ": nf must be in [2, 64], got ", nf);
+  CHK(K == 4 || K == 8 || K == 16 || K == 32 || K == 64, op,
+      ": K must be 4, 8, 16, 32 or 64, got ", K);
+  CHK(nf * K <= 1024, op, ": nf*K must be at most 1024, got ", nf * K);
+  const int64_t Dz = lightctr::pnn_out_dim((int)nf, (int)K);
+  CHK(B * Dz < (int64_t(1) << 31), op, ": B*Dz must be below 2^31, got ",
+      B * Dz);
+  return Dz;
+}
+
+void check_pnn_tensor(const at::Tensor& t, at::ScalarType dt, int64_t width,
+                      const char* name, const char* what, const char* op) {
+  CHK(t.is_cuda(), op, ": ", name, " must be on GPU");
+  CHK(t.scalar_type() == dt, op, ": ", name, " must be ",
+      dt == at::kFloat ? "fp32" : "bf16");
+  CHK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+  CHK(t.dim() == 2 && t.size(1) == width, op, ": ", name, " must be [B, ",
+      what, " = ", width, "], got width ", t.dim() == 2 ? t.size(1) : -1);
+  CHK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+      " must be 16-byte aligned");
+}
+
+// z bf16 [B, Dz] = [x0 | the nf (nf-1)/2 pair inner products | +0]
+at::Tensor pnn_forward(at::Tensor x0, int64_t nf) {
+  const char* op = "pnn_forward";
+  CHK(nf >= 2 && nf <= 64, op, ": nf must be in [2, 64], got ", nf);
+  CHK(x0.dim() == 2 && x0.size(1) % nf == 0, op,
+      ": x0 must be [B, nf*K] with nf = ", nf, ", got width ",
+      x0.dim() == 2 ? x0.size(1) : -1);
+  const int64_t K = x0.size(1) / nf, B = x0.size(0);
+  const int64_t Dz = check_pnn_dims(nf, K, B, op);
+  check_pnn_tensor(x0, at::kBFloat16, nf * K, "x0", "nf*K", op);
+  auto z = at::empty({B, Dz}, x0.options());
+  if (B > 0) {
+    lightctr::pnn_forward_launch(x0.data_ptr(), z.data_ptr(), (int)nf, (int)K,
+                                 (int)B, cur_stream());
+    C10_CUDA_KERNEL_LAUNCH_CHECK();
+  }
+  return z;
+}
+
+// dDeep fp32 [B, nf*K] from z (the forward's output) and the MLP's input
+// gradient dz fp32 [B, Dz]
+at::Tensor pnn_backward(at::Tensor z, at::Tensor dz, int64_t nf, int64_t K) {
+  const char* op = "pnn_backward";
+  const int64_t B = z.dim() == 2 ? z.size(0) : 0;
+  const int64_t Dz = check_pnn_dims(nf, K, B, op);
+  check_pnn_tensor(z, at::kBFloat16, Dz, "z", "Dz", op);
+  check_pnn_tensor(dz, at::kFloat, Dz, "dz", "Dz", op);
+  CHK(dz.size(0) == B, op, ": dz must have B = ", B, " rows, got ",
+      dz.size(0));
+  auto dDeep = at::empty({B, nf * K}, dz.options());
+  if (B > 0) {
+    lightctr::pnn_backward_launch(z.data_ptr(), dz.data_ptr<float>(),
+                                  dDeep.data_ptr<float>(), (int)nf, (int)K,
+                                  (int)B, cur_stream());
+    C10_CUDA_KERNEL_LAUNCH_CHECK();
+  }
+  return dDeep;
+}
+
 // ---- native data loader ----
 // Fast single-pass libffm parser ("label field:fid:val" per line) —
 // native equivalent of the reference's C++ loader
@@ -3211,6 +3277,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("K"), py::arg("A"));
   m.def("afm_backward_chunks", &lightctr::afm_backward_chunks,
         "partials of the AFM parameter gradients for a batch", py::arg("B"));
+  m.def("pnn_forward", &pnn_forward,
+        "PNN product layer on the bf16 concat: z bf16 [B, Dz] = [x0 | pair "
+        "inner products | +0]",
+        py::arg("x0"), py::arg("nf"));
+  m.def("pnn_backward", &pnn_backward,
+        "PNN product layer backward: dDeep fp32 [B, nf*K] from z and dz",
+        py::arg("z"), py::arg("dz"), py::arg("nf"), py::arg("K"));
+  m.def("pnn_tile_rows", &lightctr::pnn_tile_rows,
+        "examples a block of the PNN kernels takes per sweep");
+  m.def("pnn_out_dim", &lightctr::pnn_out_dim,
+        "Dz: nf*K + nf (nf-1)/2 rounded up to a multiple of 8", py::arg("nf"),
+        py::arg("K"));
   m.def("wide_forward", &wide_forward, "LR wide forward sum");
   m.def("w2v_negsample_step", &w2v_negsample_step,
         "fused CBOW negative-sampling train step (Hogwild)");

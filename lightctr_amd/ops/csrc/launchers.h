@@ -445,6 +445,17 @@ void afm_backward_launch(const void* x0, const float* lse, const float* afm,
                          float* dDeep, float* part, float* out, int nf, int K,
                          int A, int B, ihipStream_t* stream);
 
+// --- pnn_kernels.hip (inner-product layer; x0: bf16 [B, nf*K]; z: bf16
+// [B, Dz], Dz = pnn_out_dim(nf, K) = nf*K + nf (nf-1)/2 rounded up to a
+// multiple of 8; dz: fp32 [B, Dz]; 2 <= nf <= 64, K in {4, 8, 16, 32, 64},
+// nf*K <= 1024, B*Dz < 2^31; bases 16-byte aligned) ---
+int pnn_tile_rows();
+int pnn_out_dim(int nf, int K);
+void pnn_forward_launch(const void* x0, void* z, int nf, int K, int B,
+                        ihipStream_t* stream);
+void pnn_backward_launch(const void* z, const float* dz, float* dDeep, int nf,
+                         int K, int B, ihipStream_t* stream);
+
 // --- codec_kernels.hip ---
 void quantile_encode_launch(const float* x, unsigned char* code,
                             const float* table, int levels, long n,
