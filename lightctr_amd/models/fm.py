@@ -60,23 +60,36 @@ class FMModel:
     """Owns parameters + optimizer state + scratch slabs on one device."""
 
     def __init__(self, hyper: FMHyper, device: str = "cpu",
-                 max_batch_nnz: int = 1 << 22):
+                 max_batch_nnz: int = 1 << 22, pack_linear: bool = True):
         self.h = hyper
         self.device = torch.device(device)
         F, K = hyper.num_features, hyper.k
         assert K in (4, 8, 16, 32, 64), "K must divide the 64-lane wavefront"
         g = torch.Generator().manual_seed(hyper.seed)
-        self.W = torch.zeros(F, device=self.device)
+        # pack_linear: the three per-feature scalars that are always used
+        # together share one 16-byte cell lin[f] = (W, nW, zW, 0), and W, nW
+        # and zW are its column views (element stride 4): one cache line per
+        # feature instead of three, and the segment reduce moves the cell as
+        # one float4. False: three contiguous tensors.
+        self.pack_linear = bool(pack_linear)
+        if self.pack_linear:
+            self.lin = torch.zeros(F, 4, device=self.device)
+            self.W = self.lin[:, 0]
+        else:
+            self.lin = None
+            self.W = torch.zeros(F, device=self.device)
         self.V = (
             torch.randn(F, K, generator=g) * hyper.init_sigma
         ).to(self.device)
-        self.gradW = torch.zeros_like(self.W)
+        self.gradW = torch.zeros(F, device=self.device)
         self.gradV = torch.zeros_like(self.V)
         # optimizer state
-        self.nW = torch.zeros_like(self.W)
+        self.nW = (self.lin[:, 1] if self.pack_linear
+                   else torch.zeros(F, device=self.device))
         self.nV = torch.zeros_like(self.V)
         if hyper.optimizer == "ftrl":
-            self.zW = torch.zeros_like(self.W)
+            self.zW = (self.lin[:, 2] if self.pack_linear
+                       else torch.zeros(F, device=self.device))
             self.zV = torch.zeros_like(self.V)
         # touched bitmap + compaction buffers
         nwords = (F + 63) // 64
@@ -362,10 +375,17 @@ class FMModel:
 
     # -- checkpoint (reference saveModel/loadModel, fm_algo_abst.h:109-135) --
     def state_dict(self) -> dict:
-        d = {"W": self.W, "V": self.V, "nW": self.nW, "nV": self.nV,
-             "hyper": self.h.__dict__}
+        """The same keys and shapes whatever pack_linear is. Under
+        pack_linear W, nW and zW are contiguous copies, not the column views:
+        torch.save writes a view's whole storage, which would put the 4F-float
+        cell table into the file three times."""
+        def lin(t):
+            return t.contiguous() if self.pack_linear else t
+
+        d = {"W": lin(self.W), "V": self.V, "nW": lin(self.nW),
+             "nV": self.nV, "hyper": self.h.__dict__}
         if self.h.optimizer == "ftrl":
-            d["zW"], d["zV"] = self.zW, self.zV
+            d["zW"], d["zV"] = lin(self.zW), self.zV
         return d
 
     def save(self, path: str) -> None:

@@ -54,6 +54,50 @@ void check_f32_n(const at::Tensor& t, int64_t n, const char* name) {
   CHK(t.numel() == n, name, " must hold ", n, " elements, got ", t.numel());
 }
 
+// W / nW / zW of the FM ops: n fp32 device elements, either contiguous or a
+// 1-D view with a positive element stride (a column of a wider table, such
+// as FMModel's packed (W, nW, zW, 0) cells). Returns the element stride.
+int check_f32_strided(const at::Tensor& t, int64_t n, const char* name) {
+  CHK(t.is_cuda(), name, " must be on GPU");
+  CHK(t.scalar_type() == at::kFloat, name, " must be fp32");
+  CHK(t.numel() == n, name, " must hold ", n, " elements, got ", t.numel());
+  if (t.is_contiguous()) return 1;
+  CHK(t.dim() == 1 && t.stride(0) >= 1 &&
+          t.stride(0) <= std::numeric_limits<int>::max(),
+      name, " must be contiguous or a 1-D view with a positive stride");
+  return (int)t.stride(0);
+}
+
+// The linear state of an FM op; zW only where the optimizer has one.
+// cell_only: the sparse applies and the fused sorted apply take a plain
+// array or a column of a 4-float cell table and reject every other stride.
+lightctr::FmLinear check_fm_linear(const at::Tensor& W, const at::Tensor& nW,
+                                   const c10::optional<at::Tensor>& zW,
+                                   int64_t F, bool cell_only = false) {
+  lightctr::FmLinear l{W.data_ptr<float>(), nW.data_ptr<float>(), nullptr,
+                       check_f32_strided(W, F, "W"),
+                       check_f32_strided(nW, F, "nW"), 1};
+  if (zW.has_value()) {
+    l.szW = check_f32_strided(*zW, F, "zW");
+    l.zW = zW->data_ptr<float>();
+  }
+  if (cell_only) {
+    for (const int st : {l.sW, l.snW, l.szW})
+      CHK(st == 1 || st == 4,
+          "W / nW / zW must be contiguous or columns of a 4-float cell table "
+          "(element stride 4), got stride ", st);
+  }
+  // columns 0 and 1 of an aligned 4-float cell: the segment reduces move the
+  // whole cell, so the last cell's fourth float must exist
+  if (l.sW == 4 && l.snW == 4 && l.nW == l.W + 1 &&
+      reinterpret_cast<uintptr_t>(l.W) % 16 == 0) {
+    const int64_t have =
+        (int64_t)W.storage().nbytes() / 4 - W.storage_offset();
+    CHK(have >= 4 * F, "packed W / nW: the storage ends inside the last cell");
+  }
+  return l;
+}
+
 void check_i32_n(const at::Tensor& t, int64_t n, const char* name) {
   check_cuda_i32(t, name);
   CHK(t.numel() == n, name, " must hold ", n, " elements, got ", t.numel());
@@ -118,12 +162,12 @@ std::vector<at::Tensor> fm_forward(at::Tensor row_ptr, at::Tensor fids,
                                    at::Tensor V) {
   const int B = check_fm_csr(row_ptr, fids, vals);
   const int K = check_fm_v(V);
-  check_f32_n(W, V.size(0), "W");
+  const int sW = check_f32_strided(W, V.size(0), "W");
   auto pred = at::empty({B}, W.options());
   auto sumVX = at::empty({B, K}, W.options());
   if (B == 0) return {pred, sumVX};  // nothing is launched for an empty batch
   lightctr::fm_forward_launch(row_ptr.data_ptr<int>(), fids.data_ptr<int>(),
-                              vals.data_ptr<float>(), W.data_ptr<float>(),
+                              vals.data_ptr<float>(), W.data_ptr<float>(), sW,
                               V.data_ptr<float>(), pred.data_ptr<float>(),
                               sumVX.data_ptr<float>(), B, K, cur_stream());
   C10_CUDA_KERNEL_LAUNCH_CHECK();
@@ -151,7 +195,7 @@ std::vector<at::Tensor> fm_forward_train(at::Tensor row_ptr, at::Tensor fids,
                                          c10::optional<at::Tensor> reset) {
   const int B = check_fm_csr(row_ptr, fids, vals);
   const int K = check_fm_v(V);
-  check_f32_n(W, V.size(0), "W");
+  const int sW = check_f32_strided(W, V.size(0), "W");
   check_cuda_f32(label, "label");
   const long nnz = fids.numel();
   CHK(label.numel() == B, "label must have one value per row");
@@ -169,7 +213,7 @@ std::vector<at::Tensor> fm_forward_train(at::Tensor row_ptr, at::Tensor fids,
   if (B == 0) return {loss, dpred, sumVX, rec};
   lightctr::fm_forward_train_launch(
       row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
-      W.data_ptr<float>(), V.data_ptr<float>(), label.data_ptr<float>(),
+      W.data_ptr<float>(), sW, V.data_ptr<float>(), label.data_ptr<float>(),
       (float)scale, loss.data_ptr<float>(), dpred.data_ptr<float>(),
       sumVX.data_ptr<float>(), rec.data_ptr<int>(), B, K, reset_ptr,
       cur_stream());
@@ -295,8 +339,9 @@ void fm_sorted_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
       sorted_fids.data_ptr<int>(), perm_ptr,
       gw.data_ptr<float>(), gv.data_ptr<float>(), gradW.data_ptr<float>(),
       gradV.data_ptr<float>(), (unsigned long long*)touched.data_ptr(),
-      (int)sorted_fids.numel(), K, 0, nullptr, nullptr, nullptr, nullptr,
-      nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, (int)chunk,
+      (int)sorted_fids.numel(), K, 0, nullptr,
+      lightctr::FmLinear{nullptr, nullptr, nullptr, 1, 1, 1}, nullptr,
+      nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, (int)chunk,
       cur_stream());
   C10_CUDA_KERNEL_LAUNCH_CHECK();
 }
@@ -321,13 +366,10 @@ void fm_sorted_apply_fused(at::Tensor sorted_fids,
       "opt_mode 1=adagrad 2=ftrl 3=ftrlW+adagradV");
   const int64_t F = gradV.size(0);
   CHK(check_fm_v(V) == K && V.size(0) == F, "V must match gradV");
-  check_f32_n(W, F, "W");
-  check_f32_n(nW, F, "nW");
   check_f32_n(nV, F * K, "nV");
-  if (opt_mode != 1) {
-    CHK(zW.has_value(), "FTRL needs zW");
-    check_f32_n(*zW, F, "zW");
-  }
+  CHK(opt_mode == 1 || zW.has_value(), "FTRL needs zW");
+  const lightctr::FmLinear lin = check_fm_linear(
+      W, nW, opt_mode != 1 ? zW : c10::optional<at::Tensor>(), F, true);
   if (opt_mode == 2) {
     CHK(zV.has_value(), "FTRL on V needs zV");
     check_f32_n(*zV, F * K, "zV");
@@ -337,9 +379,7 @@ void fm_sorted_apply_fused(at::Tensor sorted_fids,
       sorted_fids.data_ptr<int>(), perm_ptr,
       gw.data_ptr<float>(), gv.data_ptr<float>(), gradW.data_ptr<float>(),
       gradV.data_ptr<float>(), (unsigned long long*)touched.data_ptr(),
-      (int)sorted_fids.numel(), K, (int)opt_mode, V.data_ptr<float>(),
-      W.data_ptr<float>(), nW.data_ptr<float>(),
-      zW.has_value() ? zW->data_ptr<float>() : nullptr,
+      (int)sorted_fids.numel(), K, (int)opt_mode, V.data_ptr<float>(), lin,
       nV.data_ptr<float>(),
       zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0,
       (float)p1, (float)p2, (float)p3, (float)v_lr, (float)v_eps,
@@ -380,7 +420,7 @@ std::vector<at::Tensor> segment_worklist(at::Tensor sorted_fids, int64_t cap,
 
 // Argument checks of every segment backward: slabs, spill list, parameters
 // and optimizer state
-void check_segment_state(const at::Tensor& sorted_fids,
+lightctr::FmLinear check_segment_state(const at::Tensor& sorted_fids,
                          const at::Tensor& gradW, const at::Tensor& gradV,
                          const at::Tensor& spill,
                          const at::Tensor& spill_count, const at::Tensor& W,
@@ -394,9 +434,7 @@ void check_segment_state(const at::Tensor& sorted_fids,
   check_cuda_i32(spill_count, "spill_count");
   check_cuda_f32(gradW, "gradW");
   check_cuda_f32(gradV, "gradV");
-  check_cuda_f32(W, "W");
   check_cuda_f32(V, "V");
-  check_cuda_f32(nW, "nW");
   check_cuda_f32(nV, "nV");
   const int K = check_fm_v(V);
   CHK(spill_count.numel() >= 1, "counters");
@@ -406,20 +444,19 @@ void check_segment_state(const at::Tensor& sorted_fids,
       "parameter / state / slab shapes must match");
   CHK(opt_mode == 1 || opt_mode == 2 || opt_mode == 3,
       "opt_mode 1=adagrad 2=ftrl 3=ftrlW+adagradV");
-  if (opt_mode != 1) {
-    CHK(zW.has_value(), "FTRL needs zW");
-    check_cuda_f32(*zW, "zW");
-    CHK(zW->numel() == W.numel(), "zW shape");
-  }
+  CHK(opt_mode == 1 || zW.has_value(), "FTRL needs zW");
   if (opt_mode == 2) {
     CHK(zV.has_value(), "FTRL on V needs zV");
     check_cuda_f32(*zV, "zV");
     CHK(zV->numel() == V.numel(), "zV shape");
   }
+  return check_fm_linear(W, nW,
+                         opt_mode != 1 ? zW : c10::optional<at::Tensor>(),
+                         V.size(0));
 }
 
 // The same plus the work list of the two list-fed entry sources
-void check_segment_common(const at::Tensor& sorted_fids,
+lightctr::FmLinear check_segment_common(const at::Tensor& sorted_fids,
                           const at::Tensor& piece_start,
                           const at::Tensor& n_pieces, const at::Tensor& gradW,
                           const at::Tensor& gradV, const at::Tensor& spill,
@@ -429,13 +466,15 @@ void check_segment_common(const at::Tensor& sorted_fids,
                           const c10::optional<at::Tensor>& zW,
                           const c10::optional<at::Tensor>& zV,
                           int64_t opt_mode) {
-  check_segment_state(sorted_fids, gradW, gradV, spill, spill_count, W, V, nW,
-                      nV, zW, zV, opt_mode);
+  const lightctr::FmLinear lin =
+      check_segment_state(sorted_fids, gradW, gradV, spill, spill_count, W, V,
+                          nW, nV, zW, zV, opt_mode);
   check_cuda_i32(piece_start, "piece_start");
   check_cuda_i32(n_pieces, "n_pieces");
   CHK(piece_start.numel() >= sorted_fids.numel(),
       "piece_start must hold nnz entries");
   CHK(n_pieces.numel() >= 1, "counters");
+  return lin;
 }
 
 // Segment backward: one K-lane subgroup per piece of the work list sums the
@@ -452,8 +491,9 @@ void fm_segment_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
                       c10::optional<at::Tensor> zV, int64_t opt_mode,
                       double p0, double p1, double p2, double p3, double v_lr,
                       double v_eps, double v_l2) {
-  check_segment_common(sorted_fids, piece_start, n_pieces, gradW, gradV, spill,
-                       spill_count, W, V, nW, nV, zW, zV, opt_mode);
+  const lightctr::FmLinear lin = check_segment_common(
+      sorted_fids, piece_start, n_pieces, gradW, gradV, spill, spill_count, W,
+      V, nW, nV, zW, zV, opt_mode);
   check_cuda_f32(gw, "gw");
   check_cuda_f32(gv, "gv");
   const long nnz = sorted_fids.numel();
@@ -473,9 +513,8 @@ void fm_segment_apply(at::Tensor sorted_fids, c10::optional<at::Tensor> perm,
       n_pieces.data_ptr<int>(), gw.data_ptr<float>(), gv.data_ptr<float>(),
       gradW.data_ptr<float>(), gradV.data_ptr<float>(),
       spill.data_ptr<int>(), spill_count.data_ptr<int>(), (int)spill.numel(),
-      (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), W.data_ptr<float>(),
-      nW.data_ptr<float>(),
-      zW.has_value() ? zW->data_ptr<float>() : nullptr, nV.data_ptr<float>(),
+      (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), lin,
+      nV.data_ptr<float>(),
       zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
       (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
       num_cus, cur_stream());
@@ -495,8 +534,9 @@ void fm_segment_apply_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
                           c10::optional<at::Tensor> zV, int64_t opt_mode,
                           double p0, double p1, double p2, double p3,
                           double v_lr, double v_eps, double v_l2) {
-  check_segment_common(sorted_fids, piece_start, n_pieces, gradW, gradV, spill,
-                       spill_count, W, V, nW, nV, zW, zV, opt_mode);
+  const lightctr::FmLinear lin = check_segment_common(
+      sorted_fids, piece_start, n_pieces, gradW, gradV, spill, spill_count, W,
+      V, nW, nV, zW, zV, opt_mode);
   const long nnz = sorted_fids.numel();
   const int K = (int)V.size(1);
   check_cuda_rec(sorted_rec, nnz, "sorted_rec");
@@ -513,9 +553,8 @@ void fm_segment_apply_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
       piece_start.data_ptr<int>(), n_pieces.data_ptr<int>(),
       gradW.data_ptr<float>(), gradV.data_ptr<float>(),
       spill.data_ptr<int>(), spill_count.data_ptr<int>(), (int)spill.numel(),
-      (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), W.data_ptr<float>(),
-      nW.data_ptr<float>(),
-      zW.has_value() ? zW->data_ptr<float>() : nullptr, nV.data_ptr<float>(),
+      (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), lin,
+      nV.data_ptr<float>(),
       zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
       (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
       num_cus, cur_stream());
@@ -535,8 +574,9 @@ void fm_segment_tile_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
                          c10::optional<at::Tensor> zV, int64_t opt_mode,
                          double p0, double p1, double p2, double p3,
                          double v_lr, double v_eps, double v_l2) {
-  check_segment_state(sorted_fids, gradW, gradV, spill, spill_count, W, V, nW,
-                      nV, zW, zV, opt_mode);
+  const lightctr::FmLinear lin =
+      check_segment_state(sorted_fids, gradW, gradV, spill, spill_count, W, V,
+                          nW, nV, zW, zV, opt_mode);
   const long tile = lightctr::fm_segment_tile();
   CHK(cap >= 1 && (cap & (cap - 1)) == 0 && cap <= tile && tile % cap == 0,
       "cap must be a power of two that divides the tile of ", tile);
@@ -565,9 +605,8 @@ void fm_segment_tile_rec(at::Tensor sorted_fids, at::Tensor sorted_rec,
       sumVX.data_ptr<float>(), dpred.data_ptr<float>(), (int)B, (int)cap,
       gradW.data_ptr<float>(), gradV.data_ptr<float>(),
       spill.data_ptr<int>(), spill_count.data_ptr<int>(), (int)spill.numel(),
-      (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), W.data_ptr<float>(),
-      nW.data_ptr<float>(),
-      zW.has_value() ? zW->data_ptr<float>() : nullptr, nV.data_ptr<float>(),
+      (int)nnz, K, (int)opt_mode, V.data_ptr<float>(), lin,
+      nV.data_ptr<float>(),
       zV.has_value() ? zV->data_ptr<float>() : nullptr, (float)p0, (float)p1,
       (float)p2, (float)p3, (float)v_lr, (float)v_eps, (float)v_l2,
       cur_stream());
@@ -1094,15 +1133,15 @@ void fm_adagrad_apply(at::Tensor uniq, at::Tensor count, at::Tensor W,
   CHK(count.numel() >= 1, "count must hold one int");
   const int K = check_fm_v(V);
   const int64_t F = V.size(0);
-  check_f32_n(W, F, "W");
-  check_f32_n(nW, F, "nW");
+  const lightctr::FmLinear lin =
+      check_fm_linear(W, nW, c10::optional<at::Tensor>(), F, true);
   check_f32_n(nV, F * K, "nV");
   check_f32_n(gradW, F, "gradW");
   check_f32_n(gradV, F * K, "gradV");
   if (uniq.numel() == 0) return;  // a grid of 0 blocks is a launch error
   lightctr::fm_adagrad_apply_launch(
-      uniq.data_ptr<int>(), count.data_ptr<int>(), W.data_ptr<float>(),
-      V.data_ptr<float>(), nW.data_ptr<float>(), nV.data_ptr<float>(),
+      uniq.data_ptr<int>(), count.data_ptr<int>(), lin,
+      V.data_ptr<float>(), nV.data_ptr<float>(),
       gradW.data_ptr<float>(), gradV.data_ptr<float>(), (float)lr, (float)eps,
       (float)l2, (int)uniq.numel(), K, cur_stream());
   C10_CUDA_KERNEL_LAUNCH_CHECK();
@@ -1119,9 +1158,7 @@ void fm_ftrl_apply(at::Tensor uniq, at::Tensor count, at::Tensor W,
   CHK(count.numel() >= 1, "count must hold one int");
   const int K = check_fm_v(V);
   const int64_t F = V.size(0);
-  check_f32_n(W, F, "W");
-  check_f32_n(zW, F, "zW");
-  check_f32_n(nW, F, "nW");
+  const lightctr::FmLinear lin = check_fm_linear(W, nW, zW, F, true);
   check_f32_n(nV, F * K, "nV");
   check_f32_n(gradW, F, "gradW");
   check_f32_n(gradV, F * K, "gradV");
@@ -1133,9 +1170,8 @@ void fm_ftrl_apply(at::Tensor uniq, at::Tensor count, at::Tensor W,
   CHK(v_adagrad != 0 || zV_ptr != nullptr, "FTRL on V needs zV");
   if (uniq.numel() == 0) return;  // a grid of 0 blocks is a launch error
   lightctr::fm_ftrl_apply_launch(
-      uniq.data_ptr<int>(), count.data_ptr<int>(), W.data_ptr<float>(),
-      V.data_ptr<float>(), zW.data_ptr<float>(), nW.data_ptr<float>(),
-      zV_ptr, nV.data_ptr<float>(), gradW.data_ptr<float>(),
+      uniq.data_ptr<int>(), count.data_ptr<int>(), lin,
+      V.data_ptr<float>(), zV_ptr, nV.data_ptr<float>(), gradW.data_ptr<float>(),
       gradV.data_ptr<float>(), (float)alpha, (float)beta, (float)l1,
       (float)l2, (int)uniq.numel(), K, (int)v_adagrad, (float)v_lr,
       (float)v_eps, (float)v_l2, cur_stream());
@@ -1528,7 +1564,7 @@ std::vector<at::Tensor> fm_forward_train_sorted(
     bool overlap) {
   check_csr_sort(row_ptr, fids, vals, end_bit, status);
   const int K = check_fm_v(V);
-  check_f32_n(W, V.size(0), "W");
+  const int sW = check_f32_strided(W, V.size(0), "W");
   check_cuda_f32(label, "label");
   const int B = (int)row_ptr.numel() - 1;
   const long nnz = fids.numel();
@@ -1548,9 +1584,10 @@ std::vector<at::Tensor> fm_forward_train_sorted(
   const auto forward = [&](ihipStream_t* stream) {
     lightctr::fm_forward_train_launch(
         row_ptr.data_ptr<int>(), fids.data_ptr<int>(), vals.data_ptr<float>(),
-        W.data_ptr<float>(), V.data_ptr<float>(), label.data_ptr<float>(),
-        (float)scale, loss.data_ptr<float>(), dpred.data_ptr<float>(),
-        sumVX.data_ptr<float>(), nullptr, B, K, reset_ptr, stream);
+        W.data_ptr<float>(), sW, V.data_ptr<float>(),
+        label.data_ptr<float>(), (float)scale, loss.data_ptr<float>(),
+        dpred.data_ptr<float>(), sumVX.data_ptr<float>(), nullptr, B, K,
+        reset_ptr, stream);
   };
   if (nnz == 0) {  // rows without entries: a loss, nothing to sort
     forward(cur_stream());

@@ -15,8 +15,10 @@
 // All buffers live in HBM3E; the whole step is 5 kernel launches and is
 // hipGraph-capturable (no device->host syncs).
 #include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include "common.h"
+#include "launchers.h"  // FmLinear
 
 namespace lightctr {
 
@@ -82,6 +84,7 @@ struct FmOptArgs {
   float* W;
   float* nW;
   float* zW;
+  int sW, snW, szW;  // element strides of W / nW / zW (FmLinear)
   float* nV;
   float* zV;
   float p0, p1, p2, p3;  // adagrad: lr, eps, l2 | ftrl: alpha, beta, l1, l2
@@ -111,6 +114,59 @@ __device__ __forceinline__ void fm_opt_step_w(int opt_mode, float& w,
   }
 }
 
+// How a kernel addresses the linear state W / nW / zW of a fid. Flat: three
+// plain arrays, element fid (the code as it was before strides existed).
+// Strided: element fid * stride, a stride per array. Cell: the three sit in
+// one 16-byte aligned (W, nW, zW, pad) cell per fid and move as one float4;
+// only the two segment reduces have this path, the launcher picks it
+// (fm_lin_mode).
+constexpr int kFmLinFlat = 0;
+constexpr int kFmLinStrided = 1;
+constexpr int kFmLinCell = 2;
+
+template <int LIN>
+__device__ __forceinline__ float* fm_lin_at(float* p, int stride, int fid) {
+  if (LIN == kFmLinFlat) return p + fid;
+  return p + (size_t)fid * (size_t)stride;
+}
+
+// pad: the cell's fourth float, carried from the load to the store. In
+// opt_mode 1 the optimizer leaves zw alone, so a cell's third float is
+// carried the same way.
+struct FmLinState {
+  float w, nw, zw, pad;
+};
+
+template <int LIN>
+__device__ __forceinline__ FmLinState fm_lin_load(const FmOptArgs& oa,
+                                                  int opt_mode, int fid) {
+  FmLinState s{0.f, 0.f, 0.f, 0.f};
+  if (LIN == kFmLinCell) {
+    const float4 c = ((const float4*)oa.W)[fid];
+    s.w = c.x;
+    s.nw = c.y;
+    s.zw = c.z;
+    s.pad = c.w;
+  } else {
+    s.w = *fm_lin_at<LIN>(oa.W, oa.sW, fid);
+    s.nw = *fm_lin_at<LIN>(oa.nW, oa.snW, fid);
+    if (opt_mode != 1) s.zw = *fm_lin_at<LIN>(oa.zW, oa.szW, fid);
+  }
+  return s;
+}
+
+template <int LIN>
+__device__ __forceinline__ void fm_lin_store(const FmOptArgs& oa, int opt_mode,
+                                             int fid, const FmLinState& s) {
+  if (LIN == kFmLinCell) {
+    ((float4*)oa.W)[fid] = make_float4(s.w, s.nw, s.zw, s.pad);
+  } else {
+    if (opt_mode != 1) *fm_lin_at<LIN>(oa.zW, oa.szW, fid) = s.zw;
+    *fm_lin_at<LIN>(oa.nW, oa.snW, fid) = s.nw;
+    *fm_lin_at<LIN>(oa.W, oa.sW, fid) = s.w;
+  }
+}
+
 // Stable logloss + upstream gradient of one row: the one place this maths
 // lives (logloss_grad_kernel and the training forward both call it).
 //   loss  = max(z,0) - z*y + log(1+exp(-|z|))
@@ -134,12 +190,17 @@ __device__ __forceinline__ void logloss_grad_row(float z, float y, float scale,
 // model and the CSR-fed sort of sort_kernels.hip makes them in registers in
 // its first pass, which lets the sort run beside a forward that has REC off.
 // Returns the row's pred (valid in every lane).
-template <int K, bool REC>
+// WS: W is read at element fid * ws (a column of a wider table); without it
+// at element fid.
+template <int K, bool REC, bool WS>
 __device__ __forceinline__ float fm_forward_row(
     const int* __restrict__ row_ptr, const int* __restrict__ fids,
-    const float* __restrict__ vals, const float* __restrict__ W,
+    const float* __restrict__ vals, const float* __restrict__ W, int ws,
     const float* __restrict__ V, float* __restrict__ sumVX,
     int2* __restrict__ rec, int row, int lane) {
+  auto w_at = [&](int f) {
+    return WS ? W[(size_t)f * (size_t)ws] : W[f];
+  };
   constexpr int G = LCTR_WAVE / K;  // features processed in parallel
   const int g = lane / K;
   const int k = lane % K;
@@ -161,7 +222,7 @@ __device__ __forceinline__ float fm_forward_row(
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       v[u] = V[(size_t)f[u] * K + k];
-      w[u] = (k == 0) ? W[f[u]] : 0.f;
+      w[u] = (k == 0) ? w_at(f[u]) : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -180,7 +241,7 @@ __device__ __forceinline__ float fm_forward_row(
     const float vx = V[(size_t)fid * K + k] * x;
     sVX += vx;
     sV2X2 += vx * vx;
-    if (k == 0) lin = fmaf(W[fid], x, lin);
+    if (k == 0) lin = fmaf(w_at(fid), x, lin);
   }
   // combine feature groups: lanes {k, K+k, 2K+k, ...} sum -> every lane
   // holds the row's total sumVX for its k (replicated G times).
@@ -193,29 +254,29 @@ __device__ __forceinline__ float fm_forward_row(
   return tot_lin + 0.5f * (tot_t - tot_v2);
 }
 
-template <int K>
+template <int K, bool WS>
 __global__ void fm_forward_kernel(const int* __restrict__ row_ptr,
                                   const int* __restrict__ fids,
                                   const float* __restrict__ vals,
-                                  const float* __restrict__ W,
+                                  const float* __restrict__ W, int ws,
                                   const float* __restrict__ V,
                                   float* __restrict__ pred,
                                   float* __restrict__ sumVX, int B) {
   const int lane = threadIdx.x & (LCTR_WAVE - 1);
   const int row = blockIdx.x * (blockDim.x / LCTR_WAVE) + (threadIdx.x >> 6);
   if (row >= B) return;
-  const float p = fm_forward_row<K, false>(row_ptr, fids, vals, W, V, sumVX,
-                                           nullptr, row, lane);
+  const float p = fm_forward_row<K, false, WS>(row_ptr, fids, vals, W, ws, V,
+                                               sumVX, nullptr, row, lane);
   if (lane == 0) pred[row] = p;
 }
 
 // Training forward: the row body above plus, in lane 0, the loss and the
 // upstream gradient of the row (what logloss_grad_kernel computes from a
 // stored pred), and, with REC, the per-entry records for the segment backward.
-template <int K, bool REC>
+template <int K, bool REC, bool WS>
 __global__ void fm_forward_train_kernel(
     const int* __restrict__ row_ptr, const int* __restrict__ fids,
-    const float* __restrict__ vals, const float* __restrict__ W,
+    const float* __restrict__ vals, const float* __restrict__ W, int ws,
     const float* __restrict__ V, const float* __restrict__ label, float scale,
     float* __restrict__ loss, float* __restrict__ dpred,
     float* __restrict__ sumVX, int2* __restrict__ rec, int B,
@@ -225,8 +286,8 @@ __global__ void fm_forward_train_kernel(
   // the spill counter of the segment backward that follows in the stream
   if (reset != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *reset = 0;
   if (row >= B) return;
-  const float p = fm_forward_row<K, REC>(row_ptr, fids, vals, W, V, sumVX,
-                                         rec, row, lane);
+  const float p = fm_forward_row<K, REC, WS>(row_ptr, fids, vals, W, ws, V,
+                                             sumVX, rec, row, lane);
   if (lane == 0) {
     float l, d;
     logloss_grad_row(p, label[row], scale, l, d);
@@ -394,7 +455,7 @@ __global__ void inv_perm_kernel(const int* __restrict__ perm,
 // 2nd arg). The K=16 walk allocates 86 VGPR — one register over the
 // 6-wave boundary (512/6 = 85.3); WPE=6 caps it at 85 for +20%
 // occupancy on this latency-bound kernel (LCTR_FM_APPLY_WPE=6 A/B).
-template <int K, bool PP = true, int WPE = 1>
+template <int K, bool PP = true, int WPE = 1, int LIN = kFmLinFlat>
 __global__ __launch_bounds__(256, WPE) void fm_sorted_apply_kernel(
     const int* __restrict__ sorted_fids, const int* __restrict__ perm,
     const float* __restrict__ gw, const float* __restrict__ gv,
@@ -436,12 +497,9 @@ __global__ __launch_bounds__(256, WPE) void fm_sorted_apply_kernel(
       oa.nV[off] = n;
       V[off] = v;
       if (k == 0) {
-        float w = oa.W[cur_fid], nw = oa.nW[cur_fid];
-        float zw = opt_mode != 1 ? oa.zW[cur_fid] : 0.f;
-        fm_opt_step_w(opt_mode, w, nw, zw, accw, oa);
-        if (opt_mode != 1) oa.zW[cur_fid] = zw;
-        oa.nW[cur_fid] = nw;
-        oa.W[cur_fid] = w;
+        FmLinState ls = fm_lin_load<LIN>(oa, opt_mode, cur_fid);
+        fm_opt_step_w(opt_mode, ls.w, ls.nw, ls.zw, accw, oa);
+        fm_lin_store<LIN>(oa, opt_mode, cur_fid, ls);
       }
     } else if (head_ok && tail_ok) {
       // exclusive owner of the whole segment: the slabs are zero for every
@@ -814,7 +872,7 @@ struct FmSrcRecompute {
 
 // D: entries per batch of the inner loop (independent gathers in flight per
 // lane). More lookahead costs registers, i.e. resident waves.
-template <int K, class Src, int D>
+template <int K, class Src, int D, int LIN>
 __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
     const int* __restrict__ sorted_fids, Src src,
     const int* __restrict__ piece_start, const int* __restrict__ n_pieces,
@@ -877,12 +935,8 @@ __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
       const bool tail = (e0 >= nnz) || (sorted_fids[e0] != fid);
       float v = V[off], n = oa.nV[off];
       float z = (opt_mode == 2) ? oa.zV[off] : 0.f;
-      float w = 0.f, nw = 0.f, zw = 0.f;
-      if (k == 0) {
-        w = oa.W[fid];
-        nw = oa.nW[fid];
-        if (opt_mode != 1) zw = oa.zW[fid];
-      }
+      FmLinState ls{0.f, 0.f, 0.f, 0.f};
+      if (k == 0) ls = fm_lin_load<LIN>(oa, opt_mode, fid);
       // rest of the piece, D independent gathers per batch; the batch's
       // handles are fetched one batch ahead, so a batch costs one round
       // trip, not handle -> data
@@ -919,10 +973,8 @@ __global__ __launch_bounds__(256) void fm_segment_apply_kernel(
         oa.nV[off] = n;
         V[off] = v;
         if (k == 0) {
-          fm_opt_step_w(opt_mode, w, nw, zw, accw, oa);
-          if (opt_mode != 1) oa.zW[fid] = zw;
-          oa.nW[fid] = nw;
-          oa.W[fid] = w;
+          fm_opt_step_w(opt_mode, ls.w, ls.nw, ls.zw, accw, oa);
+          fm_lin_store<LIN>(oa, opt_mode, fid, ls);
         }
       } else {
         atomicAdd(&gradV[off], acc);
@@ -993,7 +1045,7 @@ constexpr int kFmTilePieceBit = 1 << 30;  // list entry: unit starts a piece
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 
-template <int K, int NT, int TILE, int SPLIT, int D>
+template <int K, int NT, int TILE, int SPLIT, int D, int LIN>
 __global__ __launch_bounds__(NT) void fm_segment_tile_kernel(
     const int* __restrict__ sorted_fids, const int2* __restrict__ rec,
     const float* __restrict__ sumVX, const float* __restrict__ dpred, int B,
@@ -1123,20 +1175,16 @@ __global__ __launch_bounds__(NT) void fm_segment_tile_kernel(
   // the optimizer state of a whole piece's fid, loaded beside its V row
   struct State {
     float4 nv, z;
-    float w, nw, zw;
+    FmLinState lin;
   };
   auto load_state = [&](bool whole, int fid) {
     State s{make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f),
-            0.f, 0.f, 0.f};
+            FmLinState{0.f, 0.f, 0.f, 0.f}};
     if (whole) {
       const size_t off = (size_t)fid * L + q;
       s.nv = nV4[off];
       if (opt_mode == 2) s.z = zV4[off];
-      if (q == 0) {
-        s.w = oa.W[fid];
-        s.nw = oa.nW[fid];
-        if (opt_mode != 1) s.zw = oa.zW[fid];
-      }
+      if (q == 0) s.lin = fm_lin_load<LIN>(oa, opt_mode, fid);
     }
     return s;
   };
@@ -1156,11 +1204,9 @@ __global__ __launch_bounds__(NT) void fm_segment_tile_kernel(
       nV4[off] = nv;
       V4[off] = v;
       if (q == 0) {
-        float w = s.w, nw = s.nw, zw = s.zw;
-        fm_opt_step_w(opt_mode, w, nw, zw, accw, oa);
-        if (opt_mode != 1) oa.zW[fid] = zw;
-        oa.nW[fid] = nw;
-        oa.W[fid] = w;
+        FmLinState ls = s.lin;
+        fm_opt_step_w(opt_mode, ls.w, ls.nw, ls.zw, accw, oa);
+        fm_lin_store<LIN>(oa, opt_mode, fid, ls);
       }
     } else {
       float* g = gradV + (size_t)fid * K + 4 * q;
@@ -1320,12 +1366,13 @@ __global__ void bitmap_compact_kernel(unsigned long long* __restrict__ bitmap,
 // slabs stay clean for the next step. Launched over `capacity` (max possible
 // uniques) and guarded by *count so no host sync is needed.
 // ---------------------------------------------------------------------------
-template <int K>
+template <int K, int LIN>
 __global__ void fm_adagrad_apply_kernel(
     const int* __restrict__ uniq, const int* __restrict__ count,
     float* __restrict__ W, float* __restrict__ V, float* __restrict__ nW,
     float* __restrict__ nV, float* __restrict__ gradW,
-    float* __restrict__ gradV, float lr, float eps, float l2, int capacity) {
+    float* __restrict__ gradV, float lr, float eps, float l2, int capacity,
+    int sW, int snW) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long i = idx / K;
   const int k = (int)(idx % K);
@@ -1335,7 +1382,8 @@ __global__ void fm_adagrad_apply_kernel(
   adagrad_update(&V[off], &nV[off], gradV[off], lr, eps, l2);
   gradV[off] = 0.f;
   if (k == 0) {
-    adagrad_update(&W[fid], &nW[fid], gradW[fid], lr, eps, l2);
+    adagrad_update(fm_lin_at<LIN>(W, sW, fid), fm_lin_at<LIN>(nW, snW, fid),
+                   gradW[fid], lr, eps, l2);
     gradW[fid] = 0.f;
   }
 }
@@ -1344,14 +1392,14 @@ __global__ void fm_adagrad_apply_kernel(
 // weights W, Adagrad on the latent factors V (FTRL's L1 shrinkage starves
 // the interaction terms; measured 0.66 vs 0.79 held-out AUC uniform-FTRL
 // vs mixed on the synthetic Criteo stream).
-template <int K>
+template <int K, int LIN>
 __global__ void fm_ftrl_apply_kernel(
     const int* __restrict__ uniq, const int* __restrict__ count,
     float* __restrict__ W, float* __restrict__ V, float* __restrict__ zW,
     float* __restrict__ nW, float* __restrict__ zV, float* __restrict__ nV,
     float* __restrict__ gradW, float* __restrict__ gradV, float alpha,
     float beta, float l1, float l2, int capacity, int v_adagrad, float v_lr,
-    float v_eps, float v_l2) {
+    float v_eps, float v_l2, int sW, int snW, int szW) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long i = idx / K;
   const int k = (int)(idx % K);
@@ -1366,7 +1414,8 @@ __global__ void fm_ftrl_apply_kernel(
   }
   gradV[off] = 0.f;
   if (k == 0) {
-    ftrl_update(&W[fid], &zW[fid], &nW[fid], gradW[fid], alpha, beta, l1, l2);
+    ftrl_update(fm_lin_at<LIN>(W, sW, fid), fm_lin_at<LIN>(zW, szW, fid),
+                fm_lin_at<LIN>(nW, snW, fid), gradW[fid], alpha, beta, l1, l2);
     gradW[fid] = 0.f;
   }
 }
@@ -1376,39 +1425,82 @@ __global__ void fm_ftrl_apply_kernel(
 // ---------------------------------------------------------------------------
 static inline int waves_per_block() { return 4; }  // 256 threads
 
+// Addressing of a kernel's linear state (kFmLin*), decided once per launch.
+// Flat when every array the optimizer uses has stride 1. Cell (cell_ok: the
+// kernel has the float4 path) when the three are the columns 0..2 of one
+// 16-byte aligned 4-float cell; opt_mode 1 has no zW and the cell's third
+// float is then carried through untouched. Anything else is strided.
+static int fm_lin_mode(const FmLinear& l, int opt_mode, bool cell_ok) {
+  const bool z = opt_mode != 1;
+  if (l.sW == 1 && l.snW == 1 && (!z || l.szW == 1)) return kFmLinFlat;
+  if (cell_ok && l.sW == 4 && l.snW == 4 && l.nW == l.W + 1 &&
+      (!z || (l.szW == 4 && l.zW == l.W + 2)) &&
+      reinterpret_cast<uintptr_t>(l.W) % 16 == 0)
+    return kFmLinCell;
+  return kFmLinStrided;
+}
+
+static FmOptArgs fm_opt_args(const FmLinear& l, float* nV, float* zV, float p0,
+                             float p1, float p2, float p3, float q0, float q1,
+                             float q2) {
+  return FmOptArgs{l.W, l.nW, l.zW, l.sW, l.snW, l.szW, nV, zV,
+                   p0,  p1,   p2,   p3,   q0,    q1,    q2};
+}
+
+#define DISPATCH_LIN(MODE, CELL, ...)                                  \
+  switch (MODE) {                                                      \
+    case kFmLinFlat: { constexpr int LINC = kFmLinFlat; __VA_ARGS__; break; } \
+    case kFmLinCell: { constexpr int LINC = CELL; __VA_ARGS__; break; } \
+    default: { constexpr int LINC = kFmLinStrided; __VA_ARGS__; break; } \
+  }
+
 void fm_forward_launch(const int* row_ptr, const int* fids, const float* vals,
-                       const float* W, const float* V, float* pred,
+                       const float* W, int sW, const float* V, float* pred,
                        float* sumVX, int B, int K, hipStream_t stream) {
   if (B <= 0) return;
   const int wpb = waves_per_block();
   dim3 block(wpb * LCTR_WAVE);
   dim3 grid((B + wpb - 1) / wpb);
-  DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_kernel<KC>), grid, block, 0,
-                                   stream, row_ptr, fids, vals, W, V, pred,
-                                   sumVX, B));
+  if (sW == 1) {
+    DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_kernel<KC, false>), grid,
+                                     block, 0, stream, row_ptr, fids, vals, W,
+                                     sW, V, pred, sumVX, B));
+  } else {
+    DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_kernel<KC, true>), grid,
+                                     block, 0, stream, row_ptr, fids, vals, W,
+                                     sW, V, pred, sumVX, B));
+  }
 }
 
 void fm_forward_train_launch(const int* row_ptr, const int* fids,
-                             const float* vals, const float* W, const float* V,
-                             const float* label, float scale, float* loss,
-                             float* dpred, float* sumVX, int* rec, int B,
-                             int K, int* reset, hipStream_t stream) {
+                             const float* vals, const float* W, int sW,
+                             const float* V, const float* label, float scale,
+                             float* loss, float* dpred, float* sumVX, int* rec,
+                             int B, int K, int* reset, hipStream_t stream) {
   if (B <= 0) return;
   const int wpb = waves_per_block();
   dim3 block(wpb * LCTR_WAVE);
   dim3 grid((B + wpb - 1) / wpb);
   // rec == nullptr: the records are made elsewhere, the row body writes none
+#define LCTR_FM_FWD_TRAIN(REC, WS)                                          \
+  DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_train_kernel<KC, REC, WS>),   \
+                                   grid, block, 0, stream, row_ptr, fids,    \
+                                   vals, W, sW, V, label, scale, loss,       \
+                                   dpred, sumVX, (int2*)rec, B, reset))
   if (rec != nullptr) {
-    DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_train_kernel<KC, true>), grid,
-                                     block, 0, stream, row_ptr, fids, vals, W,
-                                     V, label, scale, loss, dpred, sumVX,
-                                     (int2*)rec, B, reset));
+    if (sW == 1) {
+      LCTR_FM_FWD_TRAIN(true, false);
+    } else {
+      LCTR_FM_FWD_TRAIN(true, true);
+    }
   } else {
-    DISPATCH_K(K, hipLaunchKernelGGL((fm_forward_train_kernel<KC, false>),
-                                     grid, block, 0, stream, row_ptr, fids,
-                                     vals, W, V, label, scale, loss, dpred,
-                                     sumVX, (int2*)nullptr, B, reset));
+    if (sW == 1) {
+      LCTR_FM_FWD_TRAIN(false, false);
+    } else {
+      LCTR_FM_FWD_TRAIN(false, true);
+    }
   }
+#undef LCTR_FM_FWD_TRAIN
 }
 
 void fm_records_launch(const int* row_ptr, const float* vals, int* rec, int B,
@@ -1468,8 +1560,8 @@ void inv_perm_launch(const int* perm, int* inv, int n, hipStream_t stream) {
 void fm_sorted_apply_launch(const int* sorted_fids, const int* perm,
                             const float* gw, const float* gv, float* gradW,
                             float* gradV, unsigned long long* touched, int nnz,
-                            int K, int opt_mode, float* V, float* W,
-                            float* nW, float* zW, float* nV, float* zV,
+                            int K, int opt_mode, float* V, FmLinear lin,
+                            float* nV, float* zV,
                             float p0, float p1, float p2, float p3,
                             float q0, float q1, float q2,
                             int chunk, hipStream_t stream) {
@@ -1525,7 +1617,22 @@ void fm_sorted_apply_launch(const int* sorted_fids, const int* perm,
   const int nwaves = (nnz + chunk - 1) / chunk;
   dim3 block(wpb * LCTR_WAVE);
   dim3 grid((nwaves + wpb - 1) / wpb);
-  FmOptArgs oa{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1, q2};
+  const FmOptArgs oa = fm_opt_args(lin, nV, zV, p0, p1, p2, p3, q0, q1, q2);
+  // opt_mode 0 touches no linear state; this walk has no cell path
+  if (opt_mode != 0 && fm_lin_mode(lin, opt_mode, false) != kFmLinFlat) {
+    if (pp) {
+      DISPATCH_K(K, hipLaunchKernelGGL(
+                        (fm_sorted_apply_kernel<KC, true, 1, kFmLinStrided>),
+                        grid, block, 0, stream, sorted_fids, perm, gw, gv,
+                        gradW, gradV, touched, nnz, chunk, opt_mode, V, oa));
+    } else {
+      DISPATCH_K(K, hipLaunchKernelGGL(
+                        (fm_sorted_apply_kernel<KC, false, 1, kFmLinStrided>),
+                        grid, block, 0, stream, sorted_fids, perm, gw, gv,
+                        gradW, gradV, touched, nnz, chunk, opt_mode, V, oa));
+    }
+    return;
+  }
   if (pp) {
     DISPATCH_K(K, hipLaunchKernelGGL((fm_sorted_apply_kernel<KC, true>),
                                      grid, block, 0, stream, sorted_fids,
@@ -1551,12 +1658,12 @@ void fm_sorted_apply_launch(const int* sorted_fids, const int* perm,
 }
 
 // resident 256-thread blocks of the segment kernel per CU (register bound)
-template <int K, class Src, int D>
+template <int K, class Src, int D, int LIN>
 static int fm_segment_blocks_per_cu() {
   static const int nb = [] {
     int n = 0;
     LCTR_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &n, fm_segment_apply_kernel<K, Src, D>,
+        &n, fm_segment_apply_kernel<K, Src, D, LIN>,
         waves_per_block() * LCTR_WAVE, 0));
     return std::max(n, 1);
   }();
@@ -1578,7 +1685,7 @@ struct FmSegmentArgs {
   int num_cus;
 };
 
-template <int K, class Src, int D>
+template <int K, class Src, int D, int LIN>
 static void fm_segment_launch_one(const FmSegmentArgs& a, const Src& src,
                                   hipStream_t stream) {
   // fixed grid: exactly the blocks the device holds at once (a block more
@@ -1586,11 +1693,11 @@ static void fm_segment_launch_one(const FmSegmentArgs& a, const Src& src,
   // possible piece
   const int wpb = waves_per_block();
   constexpr int G = LCTR_WAVE / K;
-  const int per_cu = fm_segment_blocks_per_cu<K, Src, D>();
+  const int per_cu = fm_segment_blocks_per_cu<K, Src, D, LIN>();
   const long need = ((long)a.nnz + (long)wpb * G - 1) / ((long)wpb * G);
   const int blocks = (int)std::max(
       1L, std::min(need, (long)per_cu * std::max(a.num_cus, 1)));
-  hipLaunchKernelGGL((fm_segment_apply_kernel<K, Src, D>), dim3(blocks),
+  hipLaunchKernelGGL((fm_segment_apply_kernel<K, Src, D, LIN>), dim3(blocks),
                      dim3(wpb * LCTR_WAVE), 0, stream, a.sorted_fids, src,
                      a.piece_start, a.n_pieces, a.gradW, a.gradV, a.spill,
                      a.spill_count, a.spill_cap, a.nnz, a.opt_mode, a.V,
@@ -1602,18 +1709,19 @@ void fm_segment_apply_launch(const int* sorted_fids, const int* perm,
                              const float* gw, const float* gv, float* gradW,
                              float* gradV, int* spill, int* spill_count,
                              int spill_cap, int nnz, int K, int opt_mode,
-                             float* V, float* W, float* nW, float* zW,
-                             float* nV, float* zV, float p0, float p1,
-                             float p2, float p3, float q0, float q1, float q2,
-                             int num_cus, hipStream_t stream) {
+                             float* V, FmLinear lin, float* nV, float* zV,
+                             float p0, float p1, float p2, float p3, float q0,
+                             float q1, float q2, int num_cus,
+                             hipStream_t stream) {
   if (nnz <= 0) return;
   const FmSegmentArgs a{sorted_fids, piece_start, n_pieces, gradW, gradV,
                         spill, spill_count, spill_cap, nnz, opt_mode, V,
-                        FmOptArgs{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1,
-                                  q2},
+                        fm_opt_args(lin, nV, zV, p0, p1, p2, p3, q0, q1, q2),
                         num_cus};
   const FmSrcGathered src{perm, gw, gv};
-  DISPATCH_K(K, (fm_segment_launch_one<KC, FmSrcGathered, 8>(a, src, stream)));
+  DISPATCH_LIN(fm_lin_mode(lin, opt_mode, true), kFmLinCell,
+               DISPATCH_K(K, (fm_segment_launch_one<KC, FmSrcGathered, 8, LINC>(
+                                 a, src, stream))));
 }
 
 // Batch depth of the recompute reduce. Measured at the flagship shape: 4
@@ -1625,18 +1733,20 @@ void fm_segment_recompute_launch(
     const int* sorted_fids, const int* rec, const float* sumVX,
     const float* dpred, int B, const int* piece_start, const int* n_pieces,
     float* gradW, float* gradV, int* spill, int* spill_count, int spill_cap,
-    int nnz, int K, int opt_mode, float* V, float* W, float* nW, float* zW,
-    float* nV, float* zV, float p0, float p1, float p2, float p3, float q0,
-    float q1, float q2, int num_cus, hipStream_t stream) {
+    int nnz, int K, int opt_mode, float* V, FmLinear lin, float* nV,
+    float* zV, float p0, float p1, float p2, float p3, float q0, float q1,
+    float q2, int num_cus, hipStream_t stream) {
   if (nnz <= 0 || B <= 0) return;
   const FmSegmentArgs a{sorted_fids, piece_start, n_pieces, gradW, gradV,
                         spill, spill_count, spill_cap, nnz, opt_mode, V,
-                        FmOptArgs{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1,
-                                  q2},
+                        fm_opt_args(lin, nV, zV, p0, p1, p2, p3, q0, q1, q2),
                         num_cus};
   const FmSrcRecompute src{(const int2*)rec, sumVX, dpred, B};
-  DISPATCH_K(K, (fm_segment_launch_one<KC, FmSrcRecompute, kFmRecomputeDepth>(
-                    a, src, stream)));
+  DISPATCH_LIN(
+      fm_lin_mode(lin, opt_mode, true), kFmLinCell,
+      DISPATCH_K(K, (fm_segment_launch_one<KC, FmSrcRecompute,
+                                           kFmRecomputeDepth, LINC>(
+                        a, src, stream))));
 }
 
 // Shape of the tile reduce: entries per block, longest unit, threads per
@@ -1666,12 +1776,12 @@ struct FmTileArgs {
   FmOptArgs oa;
 };
 
-template <int K, int NT, int TILE, int SPLIT, int D>
+template <int K, int NT, int TILE, int SPLIT, int D, int LIN>
 static void fm_segment_tile_launch_one(const FmTileArgs& a,
                                        hipStream_t stream) {
   // one block per tile: the count is known here, the dispatcher balances
   const int blocks = (int)(((long)a.nnz + TILE - 1) / TILE);
-  hipLaunchKernelGGL((fm_segment_tile_kernel<K, NT, TILE, SPLIT, D>),
+  hipLaunchKernelGGL((fm_segment_tile_kernel<K, NT, TILE, SPLIT, D, LIN>),
                      dim3(blocks), dim3(NT), 0, stream, a.sorted_fids,
                      (const int2*)a.rec, a.sumVX, a.dpred, a.B, a.cap, a.gradW,
                      a.gradV, a.spill, a.spill_count, a.spill_cap, a.nnz,
@@ -1686,18 +1796,19 @@ void fm_segment_tile_launch(const int* sorted_fids, const int* rec,
                             const float* sumVX, const float* dpred, int B,
                             int cap, float* gradW, float* gradV, int* spill,
                             int* spill_count, int spill_cap, int nnz, int K,
-                            int opt_mode, float* V, float* W, float* nW,
-                            float* zW, float* nV, float* zV, float p0,
-                            float p1, float p2, float p3, float q0, float q1,
-                            float q2, hipStream_t stream) {
+                            int opt_mode, float* V, FmLinear lin, float* nV,
+                            float* zV, float p0, float p1, float p2, float p3,
+                            float q0, float q1, float q2,
+                            hipStream_t stream) {
   if (nnz <= 0 || B <= 0) return;
   const FmTileArgs a{sorted_fids, rec, sumVX, dpred, B, cap, gradW, gradV,
                      spill, spill_count, spill_cap, nnz, opt_mode, V,
-                     FmOptArgs{W, nW, zW, nV, zV, p0, p1, p2, p3, q0, q1,
-                               q2}};
-  DISPATCH_K(K, (fm_segment_tile_launch_one<KC, kFmTileThreads, kFmTile,
-                                            kFmTileSplit, kFmTileDepth>(
-                    a, stream)));
+                     fm_opt_args(lin, nV, zV, p0, p1, p2, p3, q0, q1, q2)};
+  DISPATCH_LIN(
+      fm_lin_mode(lin, opt_mode, true), kFmLinCell,
+      DISPATCH_K(K, (fm_segment_tile_launch_one<KC, kFmTileThreads, kFmTile,
+                                                kFmTileSplit, kFmTileDepth,
+                                                LINC>(a, stream))));
 }
 
 void bitmap_compact_launch(unsigned long long* bitmap, int nwords,
@@ -1709,20 +1820,23 @@ void bitmap_compact_launch(unsigned long long* bitmap, int nwords,
                      nwords, out_fids, out_count, cap);
 }
 
-void fm_adagrad_apply_launch(const int* uniq, const int* count, float* W,
-                             float* V, float* nW, float* nV, float* gradW,
+void fm_adagrad_apply_launch(const int* uniq, const int* count, FmLinear lin,
+                             float* V, float* nV, float* gradW,
                              float* gradV, float lr, float eps, float l2,
                              int capacity, int K, hipStream_t stream) {
   const long long total = (long long)capacity * K;
   dim3 block(256);
   dim3 grid((unsigned)((total + 255) / 256));
-  DISPATCH_K(K, hipLaunchKernelGGL((fm_adagrad_apply_kernel<KC>), grid, block,
-                                   0, stream, uniq, count, W, V, nW, nV, gradW,
-                                   gradV, lr, eps, l2, capacity));
+  DISPATCH_LIN(fm_lin_mode(lin, 1, false), kFmLinStrided,
+               DISPATCH_K(K, hipLaunchKernelGGL(
+                                 (fm_adagrad_apply_kernel<KC, LINC>), grid,
+                                 block, 0, stream, uniq, count, lin.W, V,
+                                 lin.nW, nV, gradW, gradV, lr, eps, l2,
+                                 capacity, lin.sW, lin.snW)));
 }
 
-void fm_ftrl_apply_launch(const int* uniq, const int* count, float* W,
-                          float* V, float* zW, float* nW, float* zV, float* nV,
+void fm_ftrl_apply_launch(const int* uniq, const int* count, FmLinear lin,
+                          float* V, float* zV, float* nV,
                           float* gradW, float* gradV, float alpha, float beta,
                           float l1, float l2, int capacity, int K,
                           int v_adagrad, float v_lr, float v_eps, float v_l2,
@@ -1730,10 +1844,13 @@ void fm_ftrl_apply_launch(const int* uniq, const int* count, float* W,
   const long long total = (long long)capacity * K;
   dim3 block(256);
   dim3 grid((unsigned)((total + 255) / 256));
-  DISPATCH_K(K, hipLaunchKernelGGL((fm_ftrl_apply_kernel<KC>), grid, block, 0,
-                                   stream, uniq, count, W, V, zW, nW, zV, nV,
-                                   gradW, gradV, alpha, beta, l1, l2,
-                                   capacity, v_adagrad, v_lr, v_eps, v_l2));
+  DISPATCH_LIN(fm_lin_mode(lin, 2, false), kFmLinStrided,
+               DISPATCH_K(K, hipLaunchKernelGGL(
+                                 (fm_ftrl_apply_kernel<KC, LINC>), grid, block,
+                                 0, stream, uniq, count, lin.W, V, lin.zW,
+                                 lin.nW, zV, nV, gradW, gradV, alpha, beta, l1,
+                                 l2, capacity, v_adagrad, v_lr, v_eps, v_l2,
+                                 lin.sW, lin.snW, lin.szW)));
 }
 
 }  // namespace lightctr

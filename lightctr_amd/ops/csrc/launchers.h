@@ -8,8 +8,18 @@ struct ihipStream_t;
 namespace lightctr {
 
 // --- fm_kernels.hip ---
+// The linear state of the FM kernels, W / nW / zW, with an element stride
+// each: 1 for a plain array, 4 for a column of the packed (W, nW, zW, 0)
+// cell. zW is nullptr where the optimizer has none. The forwards take W's
+// stride alone (sW).
+struct FmLinear {
+  float* W;
+  float* nW;
+  float* zW;
+  int sW, snW, szW;
+};
 void fm_forward_launch(const int* row_ptr, const int* fids, const float* vals,
-                       const float* W, const float* V, float* pred,
+                       const float* W, int sW, const float* V, float* pred,
                        float* sumVX, int B, int K, ihipStream_t* stream);
 void logloss_grad_launch(const float* pred, const float* label, float* loss,
                          float* dpred, float scale, int B,
@@ -27,8 +37,8 @@ void inv_perm_launch(const int* perm, int* inv, int n, ihipStream_t* stream);
 void fm_sorted_apply_launch(const int* sorted_fids, const int* perm,
                             const float* gw, const float* gv, float* gradW,
                             float* gradV, unsigned long long* touched, int nnz,
-                            int K, int opt_mode, float* V, float* W,
-                            float* nW, float* zW, float* nV, float* zV,
+                            int K, int opt_mode, float* V, FmLinear lin,
+                            float* nV, float* zV,
                             float p0, float p1, float p2, float p3,
                             float q0, float q1, float q2,
                             int chunk, ihipStream_t* stream);
@@ -37,15 +47,16 @@ void fm_segment_apply_launch(const int* sorted_fids, const int* perm,
                              const float* gw, const float* gv, float* gradW,
                              float* gradV, int* spill, int* spill_count,
                              int spill_cap, int nnz, int K, int opt_mode,
-                             float* V, float* W, float* nW, float* zW,
-                             float* nV, float* zV, float p0, float p1,
-                             float p2, float p3, float q0, float q1, float q2,
-                             int num_cus, ihipStream_t* stream);
+                             float* V, FmLinear lin, float* nV, float* zV,
+                             float p0, float p1, float p2, float p3, float q0,
+                             float q1, float q2, int num_cus,
+                             ihipStream_t* stream);
 // rec: [n, 2] int32 records {row, bits of x}, 8-byte aligned; nullptr: the
 // forward writes no records (fm_records_launch or the CSR sort makes them)
 void fm_forward_train_launch(const int* row_ptr, const int* fids,
-                             const float* vals, const float* W, const float* V,
-                             const float* label, float scale, float* loss,
+                             const float* vals, const float* W, int sW,
+                             const float* V, const float* label, float scale,
+                             float* loss,
                              float* dpred, float* sumVX, int* rec, int B,
                              int K, int* reset, ihipStream_t* stream);
 void fm_records_launch(const int* row_ptr, const float* vals, int* rec, int B,
@@ -54,9 +65,9 @@ void fm_segment_recompute_launch(
     const int* sorted_fids, const int* rec, const float* sumVX,
     const float* dpred, int B, const int* piece_start, const int* n_pieces,
     float* gradW, float* gradV, int* spill, int* spill_count, int spill_cap,
-    int nnz, int K, int opt_mode, float* V, float* W, float* nW, float* zW,
-    float* nV, float* zV, float p0, float p1, float p2, float p3, float q0,
-    float q1, float q2, int num_cus, ihipStream_t* stream);
+    int nnz, int K, int opt_mode, float* V, FmLinear lin, float* nV,
+    float* zV, float p0, float p1, float p2, float p3, float q0, float q1,
+    float q2, int num_cus, ihipStream_t* stream);
 // tile-local segment reduce: needs cap <= fm_segment_tile() and the tile a
 // multiple of cap; no work list
 int fm_segment_tile();
@@ -66,10 +77,10 @@ void fm_segment_tile_launch(const int* sorted_fids, const int* rec,
                             const float* sumVX, const float* dpred, int B,
                             int cap, float* gradW, float* gradV, int* spill,
                             int* spill_count, int spill_cap, int nnz, int K,
-                            int opt_mode, float* V, float* W, float* nW,
-                            float* zW, float* nV, float* zV, float p0,
-                            float p1, float p2, float p3, float q0, float q1,
-                            float q2, ihipStream_t* stream);
+                            int opt_mode, float* V, FmLinear lin, float* nV,
+                            float* zV, float p0, float p1, float p2, float p3,
+                            float q0, float q1, float q2,
+                            ihipStream_t* stream);
 void bitmap_compact_launch(unsigned long long* bitmap, int nwords,
                            int* out_fids, int* out_count, int cap,
                            ihipStream_t* stream);
@@ -159,12 +170,12 @@ void sparse_ftrl_apply_launch(const int* uniq, const int* count, float* W,
                               int capacity, int D, int v_adagrad, float v_lr,
                               float v_eps, float v_l2, void* Vh,
                               ihipStream_t* stream);
-void fm_adagrad_apply_launch(const int* uniq, const int* count, float* W,
-                             float* V, float* nW, float* nV, float* gradW,
+void fm_adagrad_apply_launch(const int* uniq, const int* count, FmLinear lin,
+                             float* V, float* nV, float* gradW,
                              float* gradV, float lr, float eps, float l2,
                              int capacity, int K, ihipStream_t* stream);
-void fm_ftrl_apply_launch(const int* uniq, const int* count, float* W,
-                          float* V, float* zW, float* nW, float* zV, float* nV,
+void fm_ftrl_apply_launch(const int* uniq, const int* count, FmLinear lin,
+                          float* V, float* zV, float* nV,
                           float* gradW, float* gradV, float alpha, float beta,
                           float l1, float l2, int capacity, int K,
                           int v_adagrad, float v_lr, float v_eps, float v_l2,
